@@ -8,7 +8,13 @@ the window, each with its own odometry error) against one shared, HBM-resident 2
 correlation grid (BASELINE.json configs[3], the configuration the metric is quoted on).  float32
 ranges, fp64 poses and the 112-byte result records are resident in HBM before the timed region.
 
-Multi-GPU: `python bench.py --gpus N` starts N ranks itself (re-exec through torch.distributed.run;
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it builds the
+workload, warms up, times the K steps, writes the last timed step's outputs if `--dump-outputs DIR` is given (pose,
+response, covariance, status, flags of every scan, as float64 .npy files) and prints the result line.  Everything
+described below that is not the headline (`roofline`, `cpu_baseline`, `sustained`, `pipelined_leg`, `plain`,
+`pruning`, `secondary`, ...) runs only with `--full`; without it those keys are null.
+
+Multi-GPU: `python bench.py --gpus N` starts N ranks itself (a torch.distributed.run child process;
 under an existing torchrun it just joins).  The scans are independent units, so the path shards with NO
 data-path collective.  Default `--scaling strong` is SURVEY §8(e)'s partition: the `--batch` (4096)
 scans are split [r*B/W, (r+1)*B/W) over the ranks (shard.shard_range); `--scaling weak` gives every
@@ -17,11 +23,11 @@ rank its own `--batch` scans.  Every rank builds the same grid from the same see
 the max-over-ranks reduction and the all_gather of the 112-byte result records ("poses out"), which is
 timed separately and reported as `gather_ms`.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the stream it
-runs on) and `cpu_baseline` (the reference's own CorrelateScan, oracle/_ref, on this box's host
+Prints ONE JSON line on rank 0; with `--full` it carries `roofline` (dominant kernel, HIP-event timed on the
+stream it runs on) and `cpu_baseline` (the reference's own CorrelateScan, oracle/_ref, on this box's host
 cores; falls back to the plain-C port where _ref is absent).
 
-At N=1 the same run also measures the other north-star configs (`secondary`, ~10 s of GPU work): config 2
+With `--full`, at N=1 the same run also measures the other north-star configs (`secondary`, ~10 s of GPU work): config 2
 (log-odds update, one scan per call and the batched entry, each against the HBM peak), config 3 (ms per complete
 MatchScan) and a closed-loop slice of config 5 (streaming front-end with its pose graph on the 4000x4000@0.025 m
 map), every one with the reference's CPU figure beside it and checked against it; plus a `sustained` leg of the
@@ -39,7 +45,9 @@ import argparse
 import json
 import os
 import pathlib
+import signal
 import socket
+import subprocess
 import sys
 import time
 
@@ -986,6 +994,15 @@ def ms_per_step_guess(nb, n_full, sec_full):
     return max(0.08, 1e3 * sec_full * nb / max(n_full, 1))
 
 
+def dump_outputs(out_dir, records):
+    """--dump-outputs: every field of the last timed step's result records (what a caller of
+    lslam_matcher_match_batch_dev_f32 receives; scan order, all ranks) as DIR/<field>.npy in float64.  4096 scans: 0.5 MB."""
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name in records.dtype.names:  # pose [n, 3], response [n], covariance [n, 3, 3], status [n], flags [n]
+        np.save(d / f"{name}.npy", np.ascontiguousarray(records[name], dtype=np.float64))
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -1031,26 +1048,42 @@ def main():
                     help="depth of the separate, labelled `pipelined_leg` (independent steps overlapping on the matcher's internal "
                          "streams: the product's option for callers whose steps do not depend on each other); 0 = skip")
     ap.add_argument("--plain-steps", type=int, default=0, help="steps of the plain (depth-1) roofline leg (0 = min(--steps, 300))")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the per-kernel profile, roofline / plain / pipelined / "
+                         "sustained legs, diagnostics, CPU baselines and the secondary configs (the --no-* options above "
+                         "and the leg sizes apply to these); without it only the K timed steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (pose, response, covariance, status, flags of every scan) "
+                         "as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     backend = os.environ.get("LSLAM_BENCH_BACKEND", "nccl")  # gloo: the N>1 control flow on a 1-GPU box (tests)
     # LSLAM_BENCH_FORCE_DIST=1: initialise torch.distributed (and run every collective of the N > 1 line) at world size 1
     # too -- how the 1-GPU test box executes the RCCL branch before an 8-GPU node does
     force_dist = os.environ.get("LSLAM_BENCH_FORCE_DIST", "0") not in ("", "0")
     depth = max(1, min(4, args.pipeline_depth))
-    leg_depth = max(0, min(4, args.pipelined_leg_depth))
+    leg_depth = max(0, min(4, args.pipelined_leg_depth)) if args.full else 0
+    diagnostics = args.full and not args.no_diagnostics
     # LSLAM_BENCH_SHARE_GPU=1 (tests only): ranks beyond the visible GPUs wrap around -- with nccl this asks RCCL for a
     # communicator with two ranks on one device, which it may refuse
     share_gpu = os.environ.get("LSLAM_BENCH_SHARE_GPU", "0") not in ("", "0")
 
     # ---- `python bench.py --gpus N`: start the N ranks ourselves ------------------------------------------------
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        have = _visible_gpus()
-        if backend == "nccl" and have < args.gpus and not share_gpu:
-            raise SystemExit(f"bench.py --gpus {args.gpus}: only {have} GPU(s) visible")
+        if backend == "nccl" and not share_gpu:
+            have = _visible_gpus()
+            if have < args.gpus:
+                raise SystemExit(f"bench.py --gpus {args.gpus}: only {have} GPU(s) visible")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(pathlib.Path(__file__).resolve()),
                *sys.argv[1:]]
-        os.execv(sys.executable, cmd)
+        # a child process, not an exec: replacing a process that has initialised the GPU (_visible_gpus) is not safe
+        child = subprocess.Popen(cmd)
+        for sig in (signal.SIGTERM, signal.SIGINT):
+            signal.signal(sig, lambda s, _f: child.send_signal(s))
+        rc = child.wait()
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1084,7 +1117,9 @@ def main():
     truth = truth_u[idx]
     odom = synth.perturb(truth, 0.3, np.deg2rad(10.0), 77)  # every problem has its own search centre
     t_gen = time.perf_counter()
-    procs = max(1, min(32, (os.cpu_count() or 1) // world_size))
+    # host processes for the ray casting (every scan has its own seeded stream: the ranges do not depend on this).  At
+    # most 16: os.cpu_count() is the whole host's, which a shared GPU node does not give to one command.
+    procs = max(1, min(16, (os.cpu_count() or 1) // world_size))
     if n_unique == n_total:
         my_ranges = cast_scans(world, laser, truth[lo:hi], lo, 555, procs)
     else:
@@ -1095,7 +1130,7 @@ def main():
 
     # ---- CPU legs: fork the workers now (no HIP / CUDA state in this process yet); they start when GO is set ------
     global GO, GO_MULTI
-    do_cpu = (not args.no_cpu) and rank == 0  # N > 1: rank 0 times the 1-core leg too (released after the timed region)
+    do_cpu = args.full and (not args.no_cpu) and rank == 0  # N > 1: rank 0 times the 1-core leg too (released after the timed region)
     do_secondary = do_cpu and not args.no_secondary and world_size == 1
     pool, tasks = None, {}
     cores = args.cpu_cores or min(os.cpu_count() or 1, 64)
@@ -1199,15 +1234,17 @@ def main():
             el = float(t.item())
         return el
 
-    # ---- untimed: one PLAIN step with HIP events around EVERY kernel (the per-kernel table, the dominant kernel's name)
     step()  # first use: allocations, the grid's derived views
-    ctx.profile(True)
-    ctx.profile_only(None)
-    ctx.profile_reset()
-    step()
-    prof_all = ctx.profile_read()
-    ctx.profile(False)
-    dom_name = max(prof_all, key=lambda k: prof_all[k][1]) if prof_all else None
+    prof_all, dom_name, prof = {}, None, {}
+    if args.full:
+        # ---- untimed: one PLAIN step with HIP events around EVERY kernel (the per-kernel table, the dominant kernel's name)
+        ctx.profile(True)
+        ctx.profile_only(None)
+        ctx.profile_reset()
+        step()
+        prof_all = ctx.profile_read()
+        ctx.profile(False)
+        dom_name = max(prof_all, key=lambda k: prof_all[k][1]) if prof_all else None
     # ---- THE CONTRACT: W untimed warm-up steps, then exactly K timed steps between barriers -- the product's pipelined
     # steps (depth D in flight on the matcher's internal streams, byte-identical records), no event anywhere in the region
     set_depth(depth)
@@ -1215,22 +1252,28 @@ def main():
         step()
     elapsed = timed(args.steps)
     local_elapsed = timed.local
+    # the records of the LAST timed step (what --dump-outputs writes and the gather below carries), copied before any
+    # later leg reuses the buffer; timed() has synchronised every stream
+    res_local = results_ring[(step_no[0] - 1) % cur_depth[0]][:n_mine].clone()
+    torch.cuda.synchronize()
     # ---- the roofline leg: the PLAIN step (depth 1, one kernel after the other on one stream -- the per-kernel
     # bookkeeping `roofline` prices), HIP events around the dominant kernel only (two events per launch cost ~3 us of
     # stream time), timed like the region above
-    set_depth(1)
-    step()
-    n_plain = args.plain_steps or min(args.steps, 300)
-    ctx.profile(True)
-    ctx.profile_only(dom_name)
-    ctx.profile_reset()
-    clk0 = ctx.clock_sample()
-    elapsed_plain = timed(n_plain)
-    clk1 = ctx.clock_sample()
-    clock_ghz = ctx.clock_ghz(clk0, clk1)  # the shader clock the leg ran at (s_memtime / s_memrealtime), not an assumed 2.4 GHz
-    ctx.profile(False)
-    prof = ctx.profile_read()  # the dominant kernel, timed live over the plain leg
-    ctx.profile_only(None)
+    n_plain, elapsed_plain, clock_ghz = 0, None, None
+    if args.full:
+        set_depth(1)
+        step()
+        n_plain = args.plain_steps or min(args.steps, 300)
+        ctx.profile(True)
+        ctx.profile_only(dom_name)
+        ctx.profile_reset()
+        clk0 = ctx.clock_sample()
+        elapsed_plain = timed(n_plain)
+        clk1 = ctx.clock_sample()
+        clock_ghz = ctx.clock_ghz(clk0, clk1)  # the shader clock the leg ran at (s_memtime / s_memrealtime), not an assumed 2.4 GHz
+        ctx.profile(False)
+        prof = ctx.profile_read()  # the dominant kernel, timed live over the plain leg
+        ctx.profile_only(None)
     # ---- the pipelined leg (labelled, never `value` unless --pipeline-depth asks for it): the same step with
     # `leg_depth` steps in flight on the matcher's internal streams
     pipelined_leg = None
@@ -1263,7 +1306,7 @@ def main():
     # ---- sustained leg: the same step for >= --sustained-s seconds (clocks ramped, visible to a 1 Hz busy sampler).
     # Reported beside `value`, never as it: `value` is the K steps of the contract above.
     sustained = None
-    if args.sustained_s > 0 and n_mine:
+    if args.full and args.sustained_s > 0 and n_mine:
         n_sus = max(args.steps, int(args.sustained_s / max(elapsed / args.steps, 1e-6)) + 1)
         el_sus = timed(n_sus)
         sustained = {"steps": n_sus, "seconds": round(el_sus, 3), "ms_per_step": round(1e3 * el_sus / n_sus, 4),
@@ -1286,7 +1329,6 @@ def main():
     barrier()
     # every buffer of the ring was written by a pipelined step of the regions above: they must all hold the same records
     ring_identical = all(bool(torch.equal(r, results)) for r in results_ring[1:])
-    res_local = results[:n_mine]
     res_np = res_local.cpu().numpy().view(api.RESULT_DTYPE).reshape(-1)
     gather_ms = None
     if distributed:
@@ -1306,7 +1348,7 @@ def main():
     # ---- untimed diagnostics: how much the exact zero-row pruning removes, and the step time without it ----------
     pruning = None
     set_depth(1)  # every diagnostic below is a plain-step measurement unless it says otherwise
-    if not args.no_diagnostics:
+    if diagnostics:
         gm.set_option("collect_stats", 1)
         step()
         ctx.synchronize()
@@ -1336,7 +1378,7 @@ def main():
     # an experiment, measured here, not used): phase B of the coarse pass reads its rows from per-drain patches of the
     # linear parity planes staged in LDS instead of gathering from the L2-resident tiled planes
     lds_experiment = None
-    if not args.no_diagnostics and n_mine >= 2048:
+    if diagnostics and n_mine >= 2048:
         try:
             gm.set_option("lds_staged", 1)
             gm.set_option("collect_stats", 1)
@@ -1371,7 +1413,7 @@ def main():
     # efficiency an N-GPU run of the timed region's depth would reach if nothing but the per-GPU step time mattered:
     # T_1(B) / (N * T(B/N)).  Records of every depth are compared with the plain step's.
     pipelined = None
-    if not args.no_diagnostics and world_size == 1 and n_mine >= 512:
+    if diagnostics and world_size == 1 and n_mine >= 512:
         try:
             pipelined = {"note": "one ScanMatcher, LSLAM_OPT_PIPELINE_DEPTH = d: d steps in flight on the matcher's internal "
                                  "streams, own per-step workspaces, shared grid; ms = wall time / steps; depth 1 = plain",
@@ -1418,6 +1460,8 @@ def main():
 
     if args.dump_results and rank == 0:
         np.save(args.dump_results, all_np.view(np.uint8).reshape(-1, 112))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, all_np)
     if rank != 0:
         gm.close()
         ctx.close()
@@ -1646,6 +1690,7 @@ def main():
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
         "scaling": args.scaling,
+        "full": args.full,
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic",
@@ -1666,7 +1711,7 @@ def main():
         # every kernel of ONE untimed plain step with HIP events around every launch (the events themselves cost ~3 us of
         # stream time per launch, so the sum exceeds a step of the timed region); the dominant kernel's figure in `roofline`
         # is the live average over the plain leg
-        "kernel_ms_one_instrumented_plain_step": {k: round(v[1], 4) for k, v in sorted(prof_all.items())},
+        "kernel_ms_one_instrumented_plain_step": {k: round(v[1], 4) for k, v in sorted(prof_all.items())} if args.full else None,
         "pruning": pruning,
         "pipelined": pipelined,
         "lds_staged_experiment": lds_experiment,
@@ -1681,7 +1726,7 @@ def main():
         "pipelined_ms_per_step": pipelined_leg["ms_per_step"] if pipelined_leg else None,
         "plain": {"steps": n_plain, "ms_per_step": round(1e3 * elapsed_plain / n_plain, 4),
                   "value": round(n_total * n_plain / elapsed_plain, 1), "unit": "scan-matches/s",
-                  "note": "the roofline leg: plain steps again, HIP events around the dominant kernel only"},
+                  "note": "the roofline leg: plain steps again, HIP events around the dominant kernel only"} if args.full else None,
         "backend": (backend if distributed else None),
         "rccl_ranks": rccl_ranks,
         "devices": device_names,

@@ -23,7 +23,7 @@ def run_bench(tmp_path, gpus, extra=(), backend=None, env_extra=None, may_fail=F
     if backend:
         env["LSLAM_BENCH_BACKEND"] = backend
     env.update(env_extra or {})
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--no-cpu",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--full", "--steps", "1", "--warmup", "1", "--no-cpu",
            "--no-diagnostics", "--batch", "1024", "--dump-results", str(out), *extra]
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -126,7 +126,7 @@ def test_n1_line_through_torchrun_equals_plain_invocation(tmp_path):
     """The driver's SCALE protocol starts every N -- N = 1 included -- through `python -m torch.distributed.run`; its BENCH
     protocol runs `python bench.py`.  The two N = 1 lines must describe the same measurement: same metric / config / leg,
     same records, `value` within the run-to-run noise of a 40-step region, and roofline + cpu_baseline present in both."""
-    common = ("--steps", "40", "--warmup", "5", "--batch", "4096", "--no-secondary", "--no-diagnostics", "--sustained-s", "0",
+    common = ("--full", "--steps", "40", "--warmup", "5", "--batch", "4096", "--no-secondary", "--no-diagnostics", "--sustained-s", "0",
               "--cpu-sample", "64", "--cpu-cores", "1")
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LSLAM_BENCH_BACKEND", "LSLAM_BENCH_FORCE_DIST",

@@ -40,7 +40,7 @@ def build(specs):
 def run(steps):
     for so in sorted(VDIR.glob("*.so")):
         env = dict(os.environ, LSLAM_GPU_LIB=str(so))
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", str(steps), "--warmup", "5", "--cpu-sample", "256",
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", str(steps), "--warmup", "5", "--cpu-sample", "256",
                             "--no-secondary", "--no-diagnostics", "--sustained-s", "0", "--plain-steps", str(steps)],
                            env=env, capture_output=True, text=True)
         try:
@@ -52,7 +52,7 @@ def run(steps):
         except Exception as e:  # noqa: BLE001
             print(so.stem, "FAILED", e, r.stderr[-400:])
         # the small per-GPU batch of an 8-GPU strong-scaling run, pipelined (depth 2) and plain
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "400", "--warmup", "20", "--batch", "512", "--no-cpu",
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "400", "--warmup", "20", "--batch", "512", "--no-cpu",
                             "--no-secondary", "--no-diagnostics", "--sustained-s", "0", "--plain-steps", "400"],
                            env=env, capture_output=True, text=True)
         try:

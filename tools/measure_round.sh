@@ -1,7 +1,7 @@
 #!/bin/bash
 # One gpurun call's worth of end-of-round evidence (run on the GPU box from the repo root):
 #   bash tools/measure_round.sh r04z
-# -> gpurun_out/<tag>/: bench.json (+ .err) = the driver's command; kernel_stats_bench_default.csv (rocprofv3 --kernel-trace
+# -> $O (the <tag> folder): bench.json (+ .err) = bench.py --full; kernel_stats_bench_default.csv (rocprofv3 --kernel-trace
 #    --stats of the same step); pmc_per_launch.json / pmc_cfg2_per_launch.json / pmc_cfg2_4000_per_launch.json (separate --pmc
 #    passes, tools/pmc_passes.sh, summarised on the box: the raw counter CSVs are too big to travel); traffic.json
 #    (tools/make_traffic.py); extra_configs.jsonl (tools/bench_extra.py: cfg 2 / 3 / 5 at full size, loop-closure matcher,
@@ -27,7 +27,7 @@ python tools/make_traffic.py $O/pmc_per_launch.json 4096 $O/pmc_cfg2_per_launch.
 # (on the box's copy of the repo; install the same files from gpurun_out/<tag>/ afterwards)
 cp $O/traffic.json profiles/traffic.json
 [ -s $O/valu_mix.json ] && cp $O/valu_mix.json profiles/valu_mix.json
-(timeout 300 python bench.py > $O/bench.json 2> $O/bench.err); echo "bench rc=$?"
+(timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err); echo "bench rc=$?"
 (timeout 200 python bench.py --steps 20 --warmup 5 > $O/bench_driver_protocol.json 2> $O/bench_driver_protocol.err); echo "bench (driver protocol) rc=$?"
 # round 6: the five-kernel step against the step kernel / multi-wave coarse blocks (measured options, default off)
 (timeout 400 python tools/step_ab.py --variants 0,3,4,104 --sizes 512,4096 > $O/step_ab.json 2> $O/step_ab.err)
@@ -39,7 +39,7 @@ cp $O/traffic.json profiles/traffic.json
 # round 6: the lone chain without the speculative anchor chains / through k_match_lone (measured option, default off)
 (LSLAM_FE_SPEC_CHAIN=0 timeout 120 python tools/chain_profile.py --scans 600 2>/dev/null | grep "^{" > $O/chain_profile_no_spec_chain.json)
 (timeout 120 python tools/chain_profile.py --scans 600 --lone-kernel 4 2>/dev/null | grep "^{" > $O/chain_profile_lone_kernel.json)
-mkdir -p gpurun_out/prof512 && (cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof512 -o s -- python $R/bench.py --batch 512 --no-cpu --no-secondary --sustained-s 0 > $O/bench_batch512.json 2> $O/bench_batch512.err)
-find gpurun_out/prof512 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats_bench_batch512.csv
-rm -rf gpurun_out/prof512
+mkdir -p $O/prof512 && (cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof512 -o s -- python $R/bench.py --full --batch 512 --no-cpu --no-secondary --sustained-s 0 > $O/bench_batch512.json 2> $O/bench_batch512.err)
+find $O/prof512 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats_bench_batch512.csv
+rm -rf $O/prof512
 ls -la $O

@@ -2,7 +2,7 @@
 #   PMC_CMD="python tools/bench_extra.py --only cfg2 --map-scans 256" PMC_OUT=pmc_cfg2 bash tools/pmc_passes.sh
 R=$GRAFT_REPO_ROOT
 OUT=${PMC_OUT:-pmc}
-CMD=${PMC_CMD:-python $R/bench.py --steps 2 --warmup 1 --no-cpu --no-diagnostics --sustained-s 0 --pipeline-depth 1 --pipelined-leg-depth 0 --plain-steps 2}
+CMD=${PMC_CMD:-python $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-diagnostics --sustained-s 0 --pipeline-depth 1 --pipelined-leg-depth 0 --plain-steps 2}
 mkdir -p $R/gpurun_out/$OUT && cd /tmp && export TMPDIR=/tmp
 # (each pass under its own timeout, with one retry: a pass that hangs must not take the passes behind it with it)
 run() {
