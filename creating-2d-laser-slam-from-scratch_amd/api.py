@@ -166,6 +166,12 @@ def deskew_scan(ctx, ranges_f32, params: DeskewParams, imu_time=None, imu_rot=No
     return xyz, valid.astype(bool)
 
 
+class GMapGeometry(C.Structure):
+    _fields_ = [("map_size_x", C.c_int32), ("map_size_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("size_x2", C.c_int32), ("size_y2", C.c_int32), ("patches_x", C.c_int32), ("patches_y", C.c_int32),
+                ("center_x", C.c_double), ("center_y", C.c_double), ("delta", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -347,6 +353,19 @@ def lib() -> C.CDLL:
     L.lslam_matcher_match_scan_cached.argtypes = [vp, vp, i32, vp, vp, i64, vp, vp, i32, vp]
     L.lslam_matcher_read_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.lslam_matcher_read_beam_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.lslam_gmap_create.argtypes = [vp, dbl, dbl, dbl, dbl, dbl, C.POINTER(vp)]
+    L.lslam_gmap_destroy.argtypes = [vp]
+    L.lslam_gmap_destroy.restype = None
+    L.lslam_gmap_info.argtypes = [vp, C.POINTER(GMapGeometry)]
+    L.lslam_gmap_set_laser.argtypes = [vp, i32, C.c_float, C.c_float, dbl, dbl]
+    L.lslam_gmap_angle_cache.argtypes = [vp, vp, vp]
+    L.lslam_gmap_reset.argtypes = [vp]
+    L.lslam_gmap_integrate.argtypes = [vp, i32, vp, vp]
+    L.lslam_gmap_compute_map.argtypes = [vp, vp, dbl, vp]
+    L.lslam_gmap_read_ros_i8.argtypes = [vp, dbl, vp]
+    L.lslam_gmap_read_counters.argtypes = [vp, vp, vp, vp]
+    L.lslam_gmap_read_patch_mask.argtypes = [vp, vp]
+    L.lslam_gmap_stats.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -1174,3 +1193,103 @@ class OccGridMap:
 
     def cells_dev_ptr(self, level: int = 0) -> int:
         return self.L.lslam_map_cells_dev_ptr(self.h, level)
+
+
+class GMappingMap:
+    """lesson4's GMapping ScanMatcherMap (hit / visit counts + float hit-position sums per cell) on the GPU, with the
+    lesson4_gmapping_node callback (gmapping.cc:127-242) as compute_map.  Ranges are float32; poses (x, y, theta)."""
+
+    NODE = dict(xmin=-40.0, ymin=-40.0, xmax=40.0, ymax=40.0, delta=0.05, max_range=30 - 0.01, max_use_range=25.0,
+                occ_thresh=0.25)  # GMapping::InitParams (gmapping.cc:44-62)
+
+    def __init__(self, ctx: Context, xmin=-40.0, ymin=-40.0, xmax=40.0, ymax=40.0, delta=0.05):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        ctx.check(ctx.L.lslam_gmap_create(ctx.h, float(xmin), float(ymin), float(xmax), float(ymax), float(delta), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        g = GMapGeometry()
+        ctx.check(ctx.L.lslam_gmap_info(self.h, C.byref(g)))
+        self.info = {k: getattr(g, k) for k, _ in GMapGeometry._fields_}
+        self.n_beams = 0
+
+    @property
+    def storage_shape(self):
+        return self.info["map_size_y"], self.info["map_size_x"]
+
+    def set_laser(self, n_beams: int, angle_min: float, angle_increment: float, max_range=30 - 0.01, max_use_range=25.0):
+        """CreateCache: the message's float32 angle fields."""
+        self.ctx.check(self.L.lslam_gmap_set_laser(self.h, int(n_beams), float(angle_min), float(angle_increment),
+                                                   float(max_range), float(max_use_range)))
+        self.n_beams = int(n_beams)
+
+    def angle_cache(self):
+        c, s = np.zeros(self.n_beams), np.zeros(self.n_beams)
+        self.ctx.check(self.L.lslam_gmap_angle_cache(self.h, c.ctypes.data, s.ctypes.data))
+        return c, s
+
+    def reset(self):
+        self.ctx.check(self.L.lslam_gmap_reset(self.h))
+
+    def _ranges(self, ranges):
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        if r.ndim == 1:
+            r = r.reshape(1, -1)
+        if r.ndim != 2 or (r.shape[0] > 0 and r.shape[1] != self.n_beams):
+            raise ValueError(f"ranges must be [n_scans, {self.n_beams}] float32")
+        return r
+
+    def integrate(self, ranges, poses=None):
+        """n_scans x n_beams readings at poses (n_scans x 3; None = all at the origin), applied in order."""
+        r = self._ranges(ranges)
+        p = None
+        if poses is not None:
+            p = _f64(poses).reshape(-1, 3)
+            if p.shape[0] != r.shape[0]:
+                raise ValueError("one pose per scan")
+        self.ctx.check(self.L.lslam_gmap_integrate(self.h, r.shape[0], r.ctypes.data, None if p is None else p.ctypes.data))
+
+    def compute_map(self, ranges, occ_thresh: float = 0.25) -> np.ndarray:
+        """The node's callback: reset, one scan at the origin, the published int8 grid [height, width]."""
+        r = self._ranges(ranges)
+        if r.shape[0] != 1:
+            raise ValueError("compute_map takes one scan")
+        out = np.empty((self.info["height"], self.info["width"]), np.int8)
+        self.ctx.check(self.L.lslam_gmap_compute_map(self.h, r.ctypes.data, float(occ_thresh), out.ctypes.data))
+        return out
+
+    def ros_i8(self, occ_thresh: float = 0.25) -> np.ndarray:
+        out = np.empty((self.info["height"], self.info["width"]), np.int8)
+        self.ctx.check(self.L.lslam_gmap_read_ros_i8(self.h, float(occ_thresh), out.ctypes.data))
+        return out
+
+    def counters(self):
+        """-> visits, n (int32), acc_x, acc_y (float32), each [map_size_y, map_size_x]"""
+        shape = self.storage_shape
+        v, n = np.empty(shape, np.int32), np.empty(shape, np.int32)
+        acc = np.empty((2,) + shape, np.float32)
+        self.ctx.check(self.L.lslam_gmap_read_counters(self.h, v.ctypes.data, n.ctypes.data, acc.ctypes.data))
+        return v, n, acc[0], acc[1]
+
+    def patch_mask(self) -> np.ndarray:
+        out = np.empty((self.info["patches_y"], self.info["patches_x"]), np.uint8)
+        self.ctx.check(self.L.lslam_gmap_read_patch_mask(self.h, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        out = np.zeros(4, np.int64)
+        self.ctx.check(self.L.lslam_gmap_stats(self.h, out.ctypes.data))
+        return dict(scans=int(out[0]), beams=int(out[1]), hits=int(out[2]), dropped=int(out[3]))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_gmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass

@@ -6,11 +6,14 @@
 //   lslam::GpuScanMatcher  <-> karto::ScanMatcher                 (Mapper.h:1127-1279)
 //   lslam::MapRepGpu       <-> hectorslam::MapRepresentationInterface (H/slam_main/
 //                              MapRepresentationInterface.h:44-69), update side
+//   lslam::GpuScanMatcherMap <-> gmapping::ScanMatcherMap        (lesson4/include/lesson4/gmapping/grid/map.h),
+//                              read side + the lesson4 GMapping node's ComputeMap
 // Only PODs appear here so the header builds without open_karto / Eigen; INTEGRATION.md shows the
 // few lines that convert karto::LocalizedRangeScan / hectorslam::DataContainer to these PODs.
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -280,6 +283,101 @@ class MapRepGpu {
  private:
   lslam_context* ctx_;
   lslam_map* h_ = nullptr;
+};
+
+// gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's
+// ComputeMap (gmapping.cc:171-242).  cell() reads from a host copy of the counters, refreshed after every change.
+struct IntPoint2 {  // gmapping::IntPoint
+  int x = 0, y = 0;
+};
+struct Point2 {  // gmapping::Point
+  double x = 0, y = 0;
+};
+struct GpuPointAccumulator {  // gmapping::PointAccumulator (map.h:17-35)
+  struct { float x = 0, y = 0; } acc;
+  int n = 0, visits = 0;
+  // visits ? n / visits : -1 (map.h:27)
+  operator double() const { return visits ? (double)n * 1 / (double)visits : -1; }
+};
+
+class GpuScanMatcherMap {
+ public:
+  // ScanMatcherMap(center, xmin, ymin, xmax, ymax, delta) with center = the box's middle (gmapping.cc:130-135)
+  GpuScanMatcherMap(lslam_context* ctx, double xmin, double ymin, double xmax, double ymax, double delta) : ctx_(ctx) {
+    int rc = lslam_gmap_create(ctx, xmin, ymin, xmax, ymax, delta, &h_);
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx));
+    lslam_gmap_info(h_, &g_);
+  }
+  ~GpuScanMatcherMap() { lslam_gmap_destroy(h_); }
+  GpuScanMatcherMap(const GpuScanMatcherMap&) = delete;
+  GpuScanMatcherMap& operator=(const GpuScanMatcherMap&) = delete;
+
+  // GMapping::CreateCache + InitParams' maxRange / maxUrange
+  void setLaser(int n_beams, float angle_min, float angle_increment, double max_range = 30 - 0.01,
+                double max_use_range = 25.0) {
+    check(lslam_gmap_set_laser(h_, n_beams, angle_min, angle_increment, max_range, max_use_range));
+  }
+  // GMapping::ComputeMap on a fresh map: the laser at (0, 0, 0)
+  void ComputeMap(const float* ranges) {
+    check(lslam_gmap_reset(h_));
+    check(lslam_gmap_integrate(h_, 1, ranges, nullptr));
+    stale_ = true;
+  }
+  // many scans at poses (x, y, theta) into this map
+  void registerScans(int n_scans, const float* ranges, const double* poses) {
+    check(lslam_gmap_integrate(h_, n_scans, ranges, poses));
+    stale_ = true;
+  }
+  // PublishMap's data: width() x height() int8
+  void publish(double occ_thresh, int8_t* out) { check(lslam_gmap_read_ros_i8(h_, occ_thresh, out)); }
+
+  int getMapSizeX() const { return g_.map_size_x; }
+  int getMapSizeY() const { return g_.map_size_y; }
+  double getDelta() const { return g_.delta; }
+  int width() const { return g_.width; }
+  int height() const { return g_.height; }
+  // Map::world2map / map2world (map.h:171-182)
+  IntPoint2 world2map(const Point2& p) const {
+    return {(int)std::round((p.x - g_.center_x) / g_.delta) + g_.size_x2,
+            (int)std::round((p.y - g_.center_y) / g_.delta) + g_.size_y2};
+  }
+  Point2 map2world(const IntPoint2& p) const {
+    return {(p.x - g_.size_x2) * g_.delta + g_.center_x, (p.y - g_.size_y2) * g_.delta + g_.center_y};
+  }
+  bool isInside(const IntPoint2& p) const { return p.x >= 0 && p.y >= 0 && p.x < g_.map_size_x && p.y < g_.map_size_y; }
+  // const Map::cell(IntPoint): the cell, or the unknown cell outside the storage
+  GpuPointAccumulator cell(const IntPoint2& p) {
+    GpuPointAccumulator c;
+    if (!isInside(p)) return c;
+    refresh();
+    const size_t i = (size_t)p.y * g_.map_size_x + p.x, cells = visits_.size();
+    c.acc.x = acc_[i];
+    c.acc.y = acc_[cells + i];
+    c.n = n_[i];
+    c.visits = visits_[i];
+    return c;
+  }
+  lslam_gmap* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  void refresh() {
+    if (!stale_) return;
+    const size_t cells = (size_t)g_.map_size_x * g_.map_size_y;
+    visits_.resize(cells);
+    n_.resize(cells);
+    acc_.resize(2 * cells);
+    check(lslam_gmap_read_counters(h_, visits_.data(), n_.data(), acc_.data()));
+    stale_ = false;
+  }
+  lslam_context* ctx_;
+  lslam_gmap* h_ = nullptr;
+  lslam_gmap_geometry g_{};
+  bool stale_ = true;
+  std::vector<int32_t> visits_, n_;
+  std::vector<float> acc_;
 };
 
 }  // namespace lslam

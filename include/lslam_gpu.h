@@ -641,6 +641,73 @@ int lslam_deskew_scan(lslam_context* ctx, const float* ranges, int n, const lsla
                       const double* imu_time, const double* imu_rot_x, const double* imu_rot_y, const double* imu_rot_z,
                       int n_imu, float* out_xyz, uint8_t* out_valid);
 
+/* ---------------------------------------------------------------------------------------- */
+/* lesson4 GMapping hit/visit count map (lesson4_gmapping_node: GMapping::ComputeMap /        */
+/* PublishMap, lesson4/src/gmapping/gmapping.cc:127-242, over ScanMatcherMap = G/map.h +      */
+/* G/harray2d.h, traced by GridLineTraversal::gridLine, G/gridlinetraversal.h; short name     */
+/* G/ = lesson4/include/lesson4/gmapping/grid/).  Storage is mapSize = (ceil(W/delta)>>5)<<5  */
+/* cells per axis in 32x32 patches; per cell visits, n (hits) and the float hit-position sum  */
+/* acc.  Pinned bit for bit (tests/test_gmapping_pin.py, tests/test_gmapping_gpu.py) against  */
+/* the reference's header classes driven through the node's callback sequence.               */
+/*  - The node publishes info.width = (uint32)((xmax - xmin) / resolution) with the float32   */
+/*    MapMetaData.resolution: 1599 for its own +-40 m / 0.05 box, one column short of the      */
+/*    1600-cell storage, and its PublishMap loop then writes data[width*y + x] past the end.  */
+/*    Here the width is taken with the double delta, (uint32)((xmax - xmin) / delta): 1600.   */
+/*  - Accumulation at poses (GMapping's registerScan use) is our contract: pose (x, y, theta) */
+/*    with c, s = sincos(theta) from the host libm, endpoint                                    */
+/*      phit.x = x + d*(c*cos_i - s*sin_i),  phit.y = y + d*(s*cos_i + c*sin_i)               */
+/*    in fp64 without contraction, p0 = world2map(x, y).  At pose (0,0,0) this IS the node's  */
+/*    phit = lp + d*(cos_i, sin_i) bit for bit (1*a - 0*b == a).  Scans apply in order: the   */
+/*    hits of scan k come before those of scan k+1 in every cell's acc sum.  Cells outside    */
+/*    [0, mapSize) are skipped and counted (the reference indexes patch (-1,-1) there).       */
+/* ---------------------------------------------------------------------------------------- */
+typedef struct lslam_gmap lslam_gmap;
+typedef struct lslam_gmap_geometry {
+  int32_t map_size_x, map_size_y; /* storage: getMapSizeX/Y (G/map.h:79-80)  */
+  int32_t width, height;          /* published nav_msgs/OccupancyGrid (see above) */
+  int32_t size_x2, size_y2;       /* m_sizeX2 = round((center - xmin)/delta) (G/map.h:141-142) */
+  int32_t patches_x, patches_y;   /* 32x32 patches (HierarchicalArray2D, G/harray2d.h:75-80) */
+  double center_x, center_y, delta;
+} lslam_gmap_geometry;
+/* ScanMatcherMap gmapping_map_(center, xmin, ymin, xmax, ymax, delta) (gmapping.cc:130-135; G/map.h:133-143).
+ * LSLAM_ERR_INVALID_ARGUMENT for delta <= 0, xmax <= xmin, ymax <= ymin or fewer than 32 cells on an axis (no patch);
+ * LSLAM_ERR_UNSUPPORTED when the published grid is narrower or lower than the storage (the node would write out of
+ * bounds) or an axis has more than 65504 cells (mapSize^2 must stay below 2^32).  All counters start at zero. */
+int lslam_gmap_create(lslam_context* ctx, double xmin, double ymin, double xmax, double ymax, double delta, lslam_gmap** out);
+void lslam_gmap_destroy(lslam_gmap* map);
+int lslam_gmap_info(const lslam_gmap* map, lslam_gmap_geometry* out);
+/* GMapping::CreateCache (gmapping.cc:112-124) + the InitParams maxRange / maxUrange (:46-49): angle_i = angle_min +
+ * i * angle_increment in FLOAT (the message's float32 fields, unsigned i), cos / sin in double by the host libm's sincos
+ * (what g++ -O2 makes of the node's cos / sin pair; glibc's sincos can differ from its cos in the last bit).  The
+ * node takes the cache from its first scan only; calling this again replaces it.  Integrating before it is
+ * LSLAM_ERR_INVALID_ARGUMENT. */
+int lslam_gmap_set_laser(lslam_gmap* map, int n_beams, float angle_min, float angle_increment, double max_range,
+                         double max_use_range);
+/* the cached cos_i / sin_i (n_beams each) */
+int lslam_gmap_angle_cache(const lslam_gmap* map, double* cos_out, double* sin_out);
+/* every counter, the patch mask and the stats back to zero (clears the marked patches only) */
+int lslam_gmap_reset(lslam_gmap* map);
+/* n_scans x n_beams float32 ranges, scan-major; poses n_scans x (x, y, theta) or NULL = all at (0, 0, 0).  Per beam
+ * (ComputeMap, gmapping.cc:171-242): skip d > maxRange, d == 0, non-finite; clamp d to maxUrange; visits++ on every
+ * gridLine(p0, p1) point but the last; if d < maxUrange a hit at p1: n++, visits++, acc += (float)phit.  Free updates of
+ * a batch come before its hits (integer counts do not care); hits add in (scan, beam) order.  At most 2^28 readings
+ * (n_scans * n_beams) per call: LSLAM_ERR_INVALID_ARGUMENT beyond; a map takes any number of calls. */
+int lslam_gmap_integrate(lslam_gmap* map, int n_scans, const float* ranges, const double* poses);
+/* GMapping::ScanCallback's map work in one call: reset + integrate one scan at the origin + read_ros_i8.
+ * out: width x height int8, row-major y * width + x. */
+int lslam_gmap_compute_map(lslam_gmap* map, const float* ranges, double occ_thresh, int8_t* out);
+/* PublishMap (gmapping.cc:141-159): storage cells -1 (visits == 0), 100 ((double)n / visits > occ_thresh), 0 otherwise;
+ * published cells beyond the storage 0 (data.resize, :80).  out: width x height int8. */
+int lslam_gmap_read_ros_i8(lslam_gmap* map, double occ_thresh, int8_t* out);
+/* map_size_x * map_size_y counters, row-major y * map_size_x + x; acc_xy = all acc.x, then all acc.y (2 x cells).
+ * Any pointer may be NULL. */
+int lslam_gmap_read_counters(lslam_gmap* map, int32_t* visits, int32_t* n, float* acc_xy);
+/* patches_y x patches_x bytes, 1 = active: the patch holds a free point of a line or a hit cell (setActiveArea,
+ * gmapping.cc:207-224) of any scan since the last reset */
+int lslam_gmap_read_patch_mask(lslam_gmap* map, uint8_t* out);
+/* since the last reset: scans, beams used (past the range filter), hits applied, cell updates dropped outside */
+int lslam_gmap_stats(lslam_gmap* map, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
