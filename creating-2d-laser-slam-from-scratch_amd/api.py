@@ -292,6 +292,13 @@ def lib() -> C.CDLL:
     L.lslam_occgrid_counters_dev_ptr.argtypes = [vp]
     L.lslam_occgrid_create_sharded.argtypes = [vp, C.POINTER(LaserParams), i32, vp, i32, vp, dbl, vp, C.POINTER(vp)]
     L.lslam_pool_occgrid_from_scans.argtypes = [vp, C.POINTER(LaserParams), i32, vp, i32, vp, dbl, C.POINTER(vp)]
+    L.lslam_frontend_livemap_create.argtypes = [vp, dbl, C.POINTER(vp)]
+    L.lslam_livemap_destroy.argtypes = [vp]
+    L.lslam_livemap_destroy.restype = None
+    L.lslam_livemap_update.argtypes = [vp]
+    L.lslam_livemap_grid.restype = vp
+    L.lslam_livemap_grid.argtypes = [vp]
+    L.lslam_livemap_stats.argtypes = [vp, vp]
     L.lslam_map_create.argtypes = [vp, i32, i32, C.c_float, C.c_float, C.c_float, i32, C.POINTER(vp)]
     L.lslam_map_destroy.argtypes = [vp]
     L.lslam_map_destroy.restype = None
@@ -851,10 +858,15 @@ class FrontEnd:
             self.ctx.check(self.L.lslam_frontend_create(matcher.h, scan_buffer_size, scan_buffer_max_distance,
                                                         min_travel_distance, min_travel_heading, C.byref(h)))
         self.h = h
+        self._livemaps = weakref.WeakSet()  # live maps read this front-end: released before it
+        self._grids = {}                    # OccupancyGrid(resolution)'s live maps, by resolution
         matcher._frontends.add(self)
 
     def close(self):
         if getattr(self, "h", None):
+            for lm in list(self._livemaps):
+                lm.close()
+            self._grids.clear()
             self.L.lslam_frontend_destroy(self.h)
             self.h = None
 
@@ -930,6 +942,15 @@ class FrontEnd:
 
     def reset(self):
         self.ctx.check(self.L.lslam_frontend_reset(self.h))
+
+    def OccupancyGrid(self, resolution: float):
+        """SlamKarto::updateMap's OccupancyGrid::CreateFromScans(GetAllProcessedScans(), resolution): the front-end's live
+        map at this resolution, brought up to date.  The grid is a view, valid until the next call."""
+        lm = self._grids.get(float(resolution))
+        if lm is None or lm.h is None:
+            lm = self._grids[float(resolution)] = LiveMap(self, resolution)
+        lm.update()
+        return lm.grid()
 
 
 class OccupancyGrid:
@@ -1037,6 +1058,66 @@ class OccupancyGrid:
         out = np.zeros((h, w), dtype=np.int8)
         self.ctx.check(self.L.lslam_occgrid_read_ros_i8(self.h, out.ctypes.data))
         return out
+
+
+class _OccupancyGridView(OccupancyGrid):
+    """An lslam_occgrid somebody else owns (a live map's): everything OccupancyGrid reads, nothing it releases."""
+
+    def __init__(self, ctx: Context, h, owner):
+        self.ctx, self.L, self.h, self._owner = ctx, ctx.L, h, owner
+
+    def close(self):
+        self.h = None
+
+
+class LiveMap:
+    """The occupancy grid of ALL the front-end's processed scans, kept up to date on the device: update() traces only the
+    scans processed since the last one unless the grid has to move (see lslam_livemap_update); after it the map equals
+    OccupancyGrid::CreateFromScans over every processed scan at its current pose."""
+
+    def __init__(self, frontend: FrontEnd, resolution: float):
+        self.fe, self.ctx, self.L = frontend, frontend.ctx, frontend.L
+        h = C.c_void_p()
+        self.ctx.check(self.L.lslam_frontend_livemap_create(frontend.h, float(resolution), C.byref(h)))
+        self.h = h
+        self._view = None
+        frontend._livemaps.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self._view is not None:
+                self._view.close()
+            self.L.lslam_livemap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:  # incl. module globals already torn down (sys is None) late in shutdown
+            pass
+
+    def update(self):
+        if self._view is not None:  # the borrowed grid is valid until the next update
+            self._view.close()
+            self._view = None
+        self.ctx.check(self.L.lslam_livemap_update(self.h))
+
+    def grid(self):
+        """The map as an OccupancyGrid (info / data / ros_data / export_counters ...) that does not own the handle; None
+        before the first update."""
+        g = self.L.lslam_livemap_grid(self.h)
+        if not g:
+            return None
+        if self._view is None or self._view.h is None:
+            self._view = _OccupancyGridView(self.ctx, C.c_void_p(g), self)
+        return self._view
+
+    def stats(self) -> dict:
+        out = np.zeros(6, dtype=np.int64)
+        self.ctx.check(self.L.lslam_livemap_stats(self.h, out.ctypes.data))
+        return dict(zip(("updates", "appends", "grows", "rebuilds", "scans_traced", "scans"), (int(v) for v in out)))
 
 
 class OccGridMap:

@@ -30,6 +30,8 @@
 #include <cfloat>
 #include <queue>
 
+#include "occgrid_impl.hpp"
+
 struct lslam_frontend_scan {
   double odom[3], robot[3], sensor[3];
   double bary[2];           // GetBarycenterPose position, or the sensor position when the scan has no filtered reading
@@ -73,6 +75,7 @@ struct lslam_frontend {
   const double* pending_ranges = nullptr;  // staged readings the next fe_match carries into HBM (its first kernel)
   std::vector<double> cos_a, sin_a;        // cos / sin of minimum_angle + i * angular_resolution
   bool have_last = false;
+  uint64_t generation = 0;                 // bumped by lslam_frontend_reset: scan ids start over (what a live map watches)
   int64_t n_chain_matches = 0, n_loop_coarse = 0, n_loop_fine = 0, n_loops_closed = 0, n_edges = 0;
   // ---- look-ahead (lslam_frontend_process_many) ---------------------------------------------------------------------
   // The loop search of scan t is a chain of lone, latency-bound matches on the loop matchers, and 98 % of them close
@@ -677,6 +680,7 @@ void lslam_frontend_destroy(lslam_frontend* f) {
 int lslam_frontend_reset(lslam_frontend* f) {
   if (!f) return LSLAM_ERR_INVALID_ARGUMENT;
   f->scans.clear();
+  f->generation++;
   f->run_start = f->run_count = 0;
   f->have_last = false;
   f->n_chain_matches = f->n_loop_coarse = f->n_loop_fine = f->n_loops_closed = f->n_edges = f->n_loop_discarded = 0;
@@ -927,3 +931,34 @@ int lslam_frontend_lookahead_stats(const lslam_frontend* f, int64_t out[3]) {
 }
 
 }  // extern "C"
+
+// ---- the live occupancy map's view of the front-end (livemap.hip, declared in occgrid_impl.hpp) ----
+namespace lslam {
+
+int frontend_view(lslam_frontend* f, FrontendView* v) {
+  lslam_matcher* m = f->m;
+  lslam_context* ctx = m->ctx;
+  LSLAM_NOT_REENTRANT(m);
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // a look-ahead match may still be moving the newest readings into their resident row: wait for it, as Process does
+  // (its record stays where Process will pick it up)
+  if (f->spec.started) fe_spec_finish(f);
+  v->ctx = ctx;
+  v->laser = &m->laser;
+  v->n_beams = m->g.n_beams;
+  v->d_ranges = f->d_ranges;
+  v->n_scans = (int)f->scans.size();
+  v->generation = f->generation;
+  return LSLAM_OK;
+}
+
+// The sensor pose the REFERENCE's scan reports: LocalizedRangeScan keeps the corrected (robot) pose and GetSensorPose
+// derives the sensor pose from it on every call (Karto.h:5280-5313), which is what Update() -- and so CreateFromScans --
+// reads.  With a laser mounted off the base centre that round trip can differ from the matched sensor pose in the last bit,
+// and the map's offset is a minimum over points computed from it.
+void frontend_sensor_poses(const lslam_frontend* f, int first, int count, double* out) {
+  for (int i = 0; i < count; i++)
+    lslam_sensor_pose_from_robot(&f->m->laser, f->scans[(size_t)first + i].robot, out + 3 * (size_t)i);
+}
+
+}  // namespace lslam

@@ -21,17 +21,11 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
-#include "karto_math.hpp"
+#include "occgrid_impl.hpp"
 
 using namespace lslam;
 
 namespace {
-
-struct OccLaser {
-  double min_angle, ang_res, min_range, max_range, range_threshold;
-  int n_beams;
-};
 
 // flags: bit0 = traced, bit1 = end point valid
 __global__ void __launch_bounds__(256)
@@ -95,14 +89,7 @@ k_occ_points(const double* __restrict__ ranges, int stride, const double* __rest
   }
 }
 
-struct OccGeom {
-  int w, h, stride;
-  double scale, ox, oy;
-};
-
-// Grid<T>::TraceLine (Karto.h:4680-4745) in closed form: with deltaY <= deltaX the error recurrence
-// "error += deltaY; if (2*error >= deltaX) { y += ystep; error -= deltaX; }" has taken
-// q(k) = floor((2*k*deltaY + deltaX) / (2*deltaX)) minor steps before point k (k = 0..deltaX).
+// one wave per beam: Grid<T>::TraceLine in closed form (occ_trace_beam, occgrid_impl.hpp)
 __global__ void __launch_bounds__(256)
 k_occ_trace(int S, OccLaser l, const double* __restrict__ poses, const double2* __restrict__ ends,
             const uint8_t* __restrict__ flags, OccGeom g, uint32_t* __restrict__ pass, uint32_t* __restrict__ hit) {
@@ -113,24 +100,10 @@ k_occ_trace(int S, OccLaser l, const double* __restrict__ poses, const double2* 
   if (!(f & 1)) return;
   const int s = (int)(beam / l.n_beams);
   // RayTrace (Karto.h:5907-5942)
-  int x0 = world_to_grid(poses[3 * s], g.ox, g.scale), y0 = world_to_grid(poses[3 * s + 1], g.oy, g.scale);
+  const int x0 = world_to_grid(poses[3 * s], g.ox, g.scale), y0 = world_to_grid(poses[3 * s + 1], g.oy, g.scale);
   const double2 e = ends[beam];
-  int x1 = world_to_grid(e.x, g.ox, g.scale), y1 = world_to_grid(e.y, g.oy, g.scale);
-  const int tx = x1, ty = y1;
-  const bool steep = abs(y1 - y0) > abs(x1 - x0);
-  if (steep) { int t = x0; x0 = y0; y0 = t; t = x1; x1 = y1; y1 = t; }
-  if (x0 > x1) { int t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t; }
-  const int dX = x1 - x0, dY = abs(y1 - y0), ystep = y0 < y1 ? 1 : -1;
-  for (int k = lane; k <= dX; k += 64) {
-    const int q = dX > 0 ? (int)((2LL * k * dY + dX) / (2LL * dX)) : 0;
-    const int x = x0 + k, y = y0 + ystep * q;
-    const int px = steep ? y : x, py = steep ? x : y;
-    if (px >= 0 && px < g.w && py >= 0 && py < g.h) atomicAdd(&pass[px + (size_t)py * g.stride], 1u);
-  }
-  if (lane == 0 && (f & 2) && tx >= 0 && tx < g.w && ty >= 0 && ty < g.h) {  // :5923-5938
-    atomicAdd(&pass[tx + (size_t)ty * g.stride], 1u);
-    atomicAdd(&hit[tx + (size_t)ty * g.stride], 1u);
-  }
+  const int x1 = world_to_grid(e.x, g.ox, g.scale), y1 = world_to_grid(e.y, g.oy, g.scale);
+  occ_trace_beam(lane, x0, y0, x1, y1, (f & 2) != 0, g, pass, hit);
 }
 
 // UpdateCell (Karto.h:5950-5965): MinPassThrough = 2, OccupancyThreshold = 0.1 (:5636-5637);
@@ -149,15 +122,6 @@ k_occ_update(OccGeom g, const uint32_t* __restrict__ pass, const uint32_t* __res
 
 }  // namespace
 
-struct lslam_occgrid {
-  lslam_context* ctx = nullptr;
-  OccGeom g{};
-  uint32_t* d_pass = nullptr;  // one allocation: pass plane, then the hit plane
-  uint32_t* d_hit = nullptr;
-  size_t cells = 0;            // stride * h words per plane
-  DevBuf<uint8_t> d_out;
-};
-
 namespace {
 
 __global__ void __launch_bounds__(256)
@@ -166,21 +130,13 @@ k_occ_add(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, size_t n
   if (i < n) dst[i] += src[i];
 }
 
-constexpr double kBoxBig = 999999999999999999.99999;  // BoundingBox2() (Karto.h:2765)
-
 // Shared body of the whole and the sharded build.  forced_box == nullptr: the grid is sized from these scans
 // (ComputeDimensions); otherwise from the given box (the union over all shards).  out == nullptr: bounds only.
 int occ_build(lslam_context* ctx, const lslam_laser* laser, int n_scans, const double* ranges, int ranges_stride,
               const double* sensor_poses, double resolution, const double* forced_box, double* box_out,
               lslam_occgrid** out) {
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  OccLaser l;
-  l.min_angle = laser->minimum_angle;
-  l.ang_res = laser->angular_resolution;
-  l.min_range = laser->minimum_range;
-  l.max_range = laser->maximum_range;
-  l.range_threshold = laser->range_threshold;
-  l.n_beams = (int)(uint32_t)kround((laser->maximum_angle - laser->minimum_angle) / laser->angular_resolution);
+  const OccLaser l = occ_laser(laser);
   const int n = l.n_beams;
   if (n_scans > 0 && ranges_stride < n)
     return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "ranges_stride %d < num_beams %d", ranges_stride, n);
@@ -230,13 +186,7 @@ int occ_build(lslam_context* ctx, const lslam_laser* laser, int n_scans, const d
   lslam_occgrid* og = new lslam_occgrid();
   og->ctx = ctx;
   OccGeom& g = og->g;
-  // ComputeDimensions (Karto.h:5799-5817)
-  g.scale = 1.0 / resolution;
-  g.w = (int)kround((bbox[2] - bbox[0]) * g.scale);
-  g.h = (int)kround((bbox[3] - bbox[1]) * g.scale);
-  g.ox = bbox[0];
-  g.oy = bbox[1];
-  g.stride = (g.w + 7) & ~7;  // Grid<kt_int32u>::Resize (Karto.h:4442)
+  g = occ_geom(bbox, resolution);  // ComputeDimensions (Karto.h:5799-5817)
   const size_t cells = (size_t)g.stride * std::max(g.h, 0);
   // one allocation, pass plane then hit plane: the sharded build all-reduces both with ONE collective
   if (hipMalloc((void**)&og->d_pass, std::max<size_t>(cells, 1) * 8) != hipSuccess) {

@@ -194,10 +194,68 @@ class GpuFrontEnd {
     if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
   }
   int RunningScans() const { return lslam_frontend_running_scans(h_); }
+  lslam_frontend* handle() const { return h_; }
+  lslam_context* context() const { return ctx_; }
 
  private:
   lslam_context* ctx_;
   lslam_frontend* h_ = nullptr;
+};
+
+// The map SlamKarto::updateMap publishes (karto_slam.cc:507-581): OccupancyGrid::CreateFromScans(
+// mapper_->GetAllProcessedScans(), resolution_) over the front-end's resident scans, kept up to date on the device
+// (lslam_livemap_*).  Update() replaces the CreateFromScans call; GetWidth / GetHeight / GetOffset and ReadRos are what
+// the callback reads afterwards (:527-569).  Declare it after the front-end it reads: it must be destroyed first.
+class LiveOccupancyGrid {
+ public:
+  LiveOccupancyGrid(GpuFrontEnd& frontEnd, double resolution) : ctx_(frontEnd.context()) {
+    int rc = lslam_frontend_livemap_create(frontEnd.handle(), resolution, &h_);
+    if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
+  }
+  ~LiveOccupancyGrid() { lslam_livemap_destroy(h_); }
+  LiveOccupancyGrid(const LiveOccupancyGrid&) = delete;
+  LiveOccupancyGrid& operator=(const LiveOccupancyGrid&) = delete;
+
+  // false where the reference's CreateFromScans returns NULL (no processed scan yet: updateMap returns false, :514-515)
+  bool Update() {
+    int rc = lslam_livemap_update(h_);
+    if (rc == LSLAM_ERR_INVALID_ARGUMENT) return false;
+    if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
+    Info();
+    return true;
+  }
+  int GetWidth() const { return dims_[0]; }
+  int GetHeight() const { return dims_[1]; }
+  // GetCoordinateConverter()->GetOffset()
+  void GetOffset(double& x, double& y) const { x = off_[0]; y = off_[1]; }
+  // nav_msgs/OccupancyGrid data as karto_slam.cc:546-569 fills it (-1 unknown, 100 occupied, 0 free), width * height
+  void ReadRos(int8_t* data) {
+    int rc = lslam_occgrid_read_ros_i8(Grid(), data);
+    if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
+  }
+  // GetValue(x, y) for every cell: GridStates (Karto.h:4193-4198)
+  void Read(uint8_t* data) {
+    int rc = lslam_occgrid_read_u8(Grid(), data);
+    if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
+  }
+  // borrowed: valid until the next Update
+  lslam_occgrid* Grid() { return lslam_livemap_grid(h_); }
+  // updates, appends, grows, rebuilds, scans traced (all updates), scans in the map
+  std::vector<int64_t> Stats() const {
+    std::vector<int64_t> s(6, 0);
+    lslam_livemap_stats(h_, s.data());
+    return s;
+  }
+
+ private:
+  void Info() {
+    double res = 0.0;
+    lslam_occgrid_info(Grid(), dims_, off_, &res);
+  }
+  lslam_context* ctx_;
+  lslam_livemap* h_ = nullptr;
+  int32_t dims_[2] = {0, 0};
+  double off_[2] = {0.0, 0.0};
 };
 
 // Batched many-scan mode over every GPU of the node (one process): scans sharded [r*B/W, (r+1)*B/W), shared grid

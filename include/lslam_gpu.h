@@ -494,6 +494,28 @@ int lslam_occgrid_create_sharded(lslam_context* ctx, const lslam_laser* laser, i
 int lslam_pool_occgrid_from_scans(lslam_pool* pool, const lslam_laser* laser, int n_scans, const double* ranges,
                                   int ranges_stride, const double* sensor_poses, double resolution, lslam_occgrid** out);
 
+/* Live map over a front-end's resident scans: what SlamKarto::updateMap (karto_slam.cc:507-581) publishes every
+ * map_update_interval, OccupancyGrid::CreateFromScans(mapper_->GetAllProcessedScans(), resolution_) (Karto.h:5659-5673),
+ * maintained incrementally.  The scans and their poses are already on the device / in the front-end: no host copy of the
+ * scans, no upload, and only the scans processed since the last update are traced unless the grid has to move (a min side
+ * of the union bounding box changed: new offset, ComputeDimensions Karto.h:5799-5817), a traced scan's pose changed, or
+ * the front-end was reset -- then all resident scans are retraced, still without an upload.  After every update the map
+ * equals CreateFromScans over all processed scans at their current poses bit for bit (integer counters).
+ * resolution 0 -> LSLAM_ERR_INVALID_ARGUMENT (Karto.h:5627-5630).  The front-end must outlive the live map. */
+typedef struct lslam_livemap lslam_livemap;
+int lslam_frontend_livemap_create(lslam_frontend* f, double resolution, lslam_livemap** out);
+void lslam_livemap_destroy(lslam_livemap* lm);
+/* SlamKarto::updateMap's CreateFromScans (karto_slam.cc:511-512).  No processed scan -> LSLAM_ERR_INVALID_ARGUMENT (the
+ * reference returns NULL, Karto.h:5661-5664); the handle stays usable.  Returns with the context stream synchronised. */
+int lslam_livemap_update(lslam_livemap* lm);
+/* the map as an ordinary lslam_occgrid (lslam_occgrid_info / _read_u8 / _read_ros_i8 / _counter_words / _export_counters /
+ * _counters_dev_ptr; karto_slam.cc:527-569 reads width, height, offset and the cells).  Borrowed: owned by the live map,
+ * valid until the next update or destroy, never to be passed to lslam_occgrid_destroy.  NULL before the first update. */
+lslam_occgrid* lslam_livemap_grid(lslam_livemap* lm);
+/* out[6] = updates, of those appends (box unchanged: new scans traced), grows (a max side moved: rows copied to the new
+ * stride, new scans traced, old scans re-traced for the cells the old bounds clipped), rebuilds (everything retraced); scans traced summed over all updates; scans in the map */
+int lslam_livemap_stats(const lslam_livemap* lm, int64_t out[6]);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Hector log-odds occupancy grid  (replaces hectorslam::OccGridMapBase<LogOddsCell,...>,    */
 /* H/map/OccGridMapBase.h, H/map/GridMapLogOdds.h, H/map/GridMapBase.h)                      */
