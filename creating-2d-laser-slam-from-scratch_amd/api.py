@@ -313,6 +313,8 @@ def lib() -> C.CDLL:
     L.lslam_map_update_by_scan_dev.argtypes = [vp, vp, i32, vp, vp]
     L.lslam_map_update_just_once.argtypes = [vp, vp, i32, vp, C.c_float, C.c_float, dbl]
     L.lslam_map_match_data.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_map_match_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_map_match_batch_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.lslam_map_cached_points.argtypes = [vp]
     L.lslam_map_set_option.argtypes = [vp, i32, i32]
     L.lslam_map_batch_stats.argtypes = [vp, vp]
@@ -1245,6 +1247,35 @@ class OccGridMap:
         self.ctx.check(self.L.lslam_map_match_data(self.h, p.ctypes.data, p.shape[0], o.ctypes.data, b.ctypes.data,
                                                    pose.ctypes.data, cov.ctypes.data))
         return pose, cov.reshape(3, 3)
+
+    def matchBatch(self, begin_world, containers, entry_container=None, counts=None):
+        """Many matchData calls against the map as it is, in one launch -> (poses[B,3], covs[B,3,3]).  `containers`: a
+        list of (n,2) float32 arrays, or -- with `counts` -- one packed (sum(counts),2) array; `entry_container[B]` names
+        each entry's container (None: entry i uses container i).  A pure query: unlike matchData it caches no container."""
+        if counts is None:
+            counts = np.array([len(p) for p in containers], dtype=np.int32)
+            pts = (np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in containers])
+                   if len(containers) else np.zeros((0, 2), np.float32))
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            pts = np.asarray(containers, dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        b = np.ascontiguousarray(begin_world, dtype=np.float32).reshape(-1, 3)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        poses, covs = np.zeros((len(b), 3), np.float32), np.zeros((len(b), 9), np.float32)
+        self.ctx.check(self.L.lslam_map_match_batch(self.h, len(b), len(counts), pts.ctypes.data, counts.ctypes.data,
+                                                    None if ec is None else ec.ctypes.data, b.ctypes.data,
+                                                    poses.ctypes.data, covs.ctypes.data))
+        return poses, covs.reshape(-1, 3, 3)
+
+    def matchBatch_dev(self, n_entries: int, points_ptr: int, counts, entry_container, begin_ptr: int, poses_ptr: int,
+                       covs_ptr: int = 0):
+        """matchBatch on device pointers (points, start poses, results in HBM); asynchronous on the context stream."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        self.ctx.check(self.L.lslam_map_match_batch_dev(self.h, n_entries, len(counts), points_ptr, counts.ctypes.data,
+                                                        None if ec is None else ec.ctypes.data, begin_ptr, poses_ptr,
+                                                        covs_ptr or None))
 
     def set_option(self, name: str, value: int):
         """'ordered_sums': matchData adds its sums in point order (bit-equal to the CPU restatement) instead of in parallel."""

@@ -702,9 +702,10 @@ __device__ __forceinline__ float gn_cof3(const float* m, int i, int j) {
   return m[3 * i1 + j1] * m[3 * i2 + j2] - m[3 * i1 + j2] * m[3 * i2 + j1];
 }
 
-__global__ void __launch_bounds__(1024)
-k_gn_match(GnLevels lv, const float* __restrict__ pts, int n, float bx, float by, float bth,
-           float* __restrict__ out /* pose[3] + H[9] */) {
+// (the body of k_gn_match; k_gn_match_batch_ordered runs the same statements with one block per entry of a batch)
+__device__ __forceinline__ void gn_match_ordered(const GnLevels& lv, const float* __restrict__ pts, int n, float bx, float by,
+                                                 float bth, float* __restrict__ out_pose /* [3] */,
+                                                 float* __restrict__ out_H /* [9], may be null */) {
   extern __shared__ float terms[];  // [n][9]
   __shared__ float s_est[3], s_sum[9];
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -798,9 +799,16 @@ k_gn_match(GnLevels lv, const float* __restrict__ pts, int n, float bx, float by
     __syncthreads();
   }
   if (tid == 0) {
-    out[0] = tmp0; out[1] = tmp1; out[2] = tmp2;
-    for (int q = 0; q < 9; q++) out[3 + q] = Hlast[q];
+    out_pose[0] = tmp0; out_pose[1] = tmp1; out_pose[2] = tmp2;
+    if (out_H)
+      for (int q = 0; q < 9; q++) out_H[q] = Hlast[q];
   }
+}
+
+__global__ void __launch_bounds__(1024)
+k_gn_match(GnLevels lv, const float* __restrict__ pts, int n, float bx, float by, float bth,
+           float* __restrict__ out /* pose[3] + H[9] */) {
+  gn_match_ordered(lv, pts, n, bx, by, bth, out, out + 3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1130,6 +1138,144 @@ k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ c
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_gn_match_batch -- MANY matchData calls against the same pyramid in one launch (lslam_map_match_batch*): entry e is
+// (container ent[e].x .. + ent[e].y of the packed points, start pose begin[e]).  Built for throughput, not latency: ONE
+// WAVE per entry, four entries per 256-thread block.  A wave needs nobody else: its nine sums meet by DPP
+// (gn_wave_sums9) and every lane solves on the broadcast totals, so there is no LDS, no barrier and no atomic, and an
+// entry's result is a function of its container, its start pose and the map only -- wherever it stands in the batch.
+// A wave walks its container from memory every iteration, kGnBatchChunk points per lane at a time (point i belongs to lane
+// i % 64; the reads are coalesced float2 and stay in L1 / L2 -- 8.6 KB for a 1081-beam scan), whatever the container's size:
+// ONE form, no switch point.  Holding a 1081-point scan in registers instead (17 points per lane, fully unrolled) was
+// tried and dropped: under the 128-VGPR cap hipcc spilled ~700 bytes per lane to scratch at every chunk size.  Each chunk is
+// k_gn_match_reg's straight-line pattern: all cell addresses, then the 4 * CH loads back to back, then the shipped per-point
+// arithmetic.  <= 128 VGPRs: four waves per SIMD stay resident and cover one another's L2 round trips, which is what bounds
+// the single-match kernel.
+// ------------------------------------------------------------------------------------------
+constexpr int kGnBatchWaves = 4;                        // entries per block
+constexpr int kGnBatchChunk = 6;  // points per lane whose four cell loads each are in flight together (384 per wave and pass)
+
+template <int CH>
+__device__ __forceinline__ void gn_batch_chunk(const float* __restrict__ lo, int sx, float lim_x, float lim_y, float s, float c,
+                                               float e0, float e1, const float* px, const float* py, const bool* have,
+                                               float* acc) {
+  int idx[CH];
+  float fx[CH], fy[CH];
+  bool inb[CH];
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    const float cx = (c * px[p] + (-s) * py[p]) + e0;
+    const float cy = (s * px[p] + c * py[p]) + e1;
+    inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
+    const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;             // (an out-of-map point reads cell 0, masked below)
+    fx[p] = cx - (float)ix;
+    fy[p] = cy - (float)iy;
+    idx[p] = iy * sx + ix;
+  }
+  float l0[CH], l1[CH], l2[CH], l3[CH];
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    l0[p] = lo[idx[p]];
+    l1[p] = lo[idx[p] + 1];
+    l2[p] = lo[idx[p] + sx];
+    l3[p] = lo[idx[p] + sx + 1];
+  }
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    const float i0 = gn_prob_f(l0[p]), i1 = gn_prob_f(l1[p]), i2 = gn_prob_f(l2[p]), i3 = gn_prob_f(l3[p]);
+    const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
+    const float xi = 1.0f - fx[p], yi = 1.0f - fy[p];
+    const float v = inb[p] ? ((i0 * xi + i1 * fx[p]) * (yi)) + ((i2 * xi + i3 * fx[p]) * (fy[p])) : 0.0f;
+    const float gxv = inb[p] ? -((dx1 * yi) + (dx2 * fy[p])) : 0.0f;
+    const float gyv = inb[p] ? -((dy1 * xi) + (dy2 * fx[p])) : 0.0f;
+    const float funVal = have[p] ? 1.0f - v : 0.0f;
+    const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
+    acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
+    acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
+    acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
+  }
+}
+
+__global__ void __launch_bounds__(64 * kGnBatchWaves) __attribute__((amdgpu_waves_per_eu(4)))
+k_gn_match_batch(GnLevels lv, const float* __restrict__ pts, const int2* __restrict__ ent /* [n_entries]: first point, points */,
+                 const float* __restrict__ begin /* [n_entries][3] */, int n_entries, float* __restrict__ out_pose /* [n_entries][3] */,
+                 float* __restrict__ out_cov /* [n_entries][9], may be null */) {
+  constexpr int CH = kGnBatchChunk;
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kGnBatchWaves + (threadIdx.x >> 6)));
+  if (e >= n_entries) return;  // (whole waves: nothing below waits for another wave)
+  const int2 en = ent[e];
+  const int first = __builtin_amdgcn_readfirstlane(en.x), n = __builtin_amdgcn_readfirstlane(en.y);
+  const float2* __restrict__ P = reinterpret_cast<const float2*>(pts) + first;
+  float tmp0 = begin[3 * e], tmp1 = begin[3 * e + 1], tmp2 = begin[3 * e + 2];
+  float H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int L = lv.n_levels - 1; L >= 0; --L) {
+    if (n == 0) continue;  // ScanMatcher.h:96: an empty container returns beginEstimateWorld as it came
+    const float* __restrict__ lo = lv.logodds[L];
+    const int sx = lv.sx[L], sy = lv.sy[L];
+    const float sc = lv.scale[L];
+    const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
+    const int iters = 1 + (L == 0 ? 5 : 3);
+    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
+    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
+    float e2 = tmp2;
+    const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
+    for (int it = 0; it < iters; it++) {
+      float s, c;
+      gn_sincos(e2, &s, &c);
+      float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int base = 0; base < n; base += 64 * CH) {  // (n is wave-uniform: no lane leaves the loop early)
+        float px[CH], py[CH];
+        bool have[CH];
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+          const int i = base + 64 * j + lane;
+          have[j] = i < n;
+          float2 v = make_float2(0.0f, 0.0f);
+          if (have[j]) v = P[i];
+          px[j] = v.x * factor;
+          py[j] = v.y * factor;
+        }
+        gn_batch_chunk<CH>(lo, sx, lim_x, lim_y, s, c, e0, e1, px, py, have, acc);
+      }
+      gn_wave_sums9(acc);  // totals in lane 63
+      float sum[9];
+#pragma unroll
+      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc[q]), 63));
+      gn_solve_step(sum, H, e0, e1, e2);
+    }
+    {
+      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
+      const double two_pi = 2.0f * 3.14159265358979323846;
+      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
+      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
+      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
+      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
+      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
+      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
+      tmp0 = (l00 * e0 + l01 * e1) + wt0;
+      tmp1 = (l10 * e0 + l11 * e1) + wt1;
+      tmp2 = a;
+    }
+  }
+  if (lane == 0) {
+    out_pose[3 * e] = tmp0; out_pose[3 * e + 1] = tmp1; out_pose[3 * e + 2] = tmp2;
+    if (out_cov)
+      for (int q = 0; q < 9; q++) out_cov[9 * e + q] = H[q];
+  }
+}
+
+// ordered sums: the single call's kernel body, one block per entry (bit-identical to lslam_map_match_data in that mode)
+__global__ void __launch_bounds__(1024)
+k_gn_match_batch_ordered(GnLevels lv, const float* __restrict__ pts, const int2* __restrict__ ent, const float* __restrict__ begin,
+                         float* __restrict__ out_pose, float* __restrict__ out_cov) {
+  const int e = blockIdx.x;
+  const int2 en = ent[e];
+  gn_match_ordered(lv, pts + 2 * (size_t)en.x, en.y, begin[3 * e], begin[3 * e + 1], begin[3 * e + 2], out_pose + 3 * (size_t)e,
+                   out_cov ? out_cov + 9 * (size_t)e : (float*)nullptr);
+}
+
+
 float prob_to_logodds(float prob) {  // H/map/GridMapLogOdds.h:151-155 (log() is the double overload)
   float odds = prob / (1.0f - prob);
   return (float)log((double)odds);
@@ -1172,6 +1318,9 @@ struct lslam_map {
   int n_cached = 0;
   float cached_origo[2] = {0.f, 0.f};
   DevBuf<float> d_gn_out;
+  // lslam_map_match_batch*: the entry table (first point, points), and -- host form -- the start poses in, 12 floats per entry out
+  DevBuf<int2> d_gnb_ent;
+  DevBuf<float> d_gnb_io;
   // matchData, parallel-sum kernel (the default): the container goes up through pinned memory and is read -- and cached in
   // d_cached -- by the kernel itself; its 12 result floats land in pinned memory.  ordered_sums: k_gn_match instead.
   // batched update: scratch budget of the tile-slot pools of ONE level (bytes), rounds used by the last call, cells
@@ -1495,6 +1644,8 @@ void lslam_map_destroy(lslam_map* map) {
   map->d_pts.release();
   map->d_cached.release();
   map->d_gn_out.release();
+  map->d_gnb_ent.release();
+  map->d_gnb_io.release();
   map->d_hash.release();
   map->d_hdr.release();
   map->d_scan.release();
@@ -2114,6 +2265,126 @@ int lslam_map_match_data(lslam_map* map, const float* pts, int n, const float or
 int lslam_map_match_container(lslam_map* map, const float begin_world[3], float out_pose[3], float out_cov[9]) {
   if (!map || !begin_world || !out_pose) return LSLAM_ERR_INVALID_ARGUMENT;
   return match_data_impl(map, map->d_scan.p, map->n_scan, true, map->scan_origo, begin_world, out_pose, out_cov);
+}
+
+namespace {
+// Many matchData calls in one launch.  Everything that can be refused is refused before anything is enqueued.  A pure
+// query: neither d_cached / n_cached (the container the next updateByScan feeds to the levels above 0) nor a plane changes.
+// d_pts: the containers back to back in HBM; begin / out_pose / out_cov (may be null) in HBM; counts / entry_container host.
+int match_batch_check(lslam_map* map, const char* who, int n_entries, int n_containers, const void* points_xy,
+                      const int32_t* n_points, const int32_t* entry_container, const void* begin_world, const void* out_poses,
+                      size_t* total_out) {
+  lslam_context* ctx = map->ctx;
+  if (n_entries < 0 || n_containers < 0)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: negative count (n_entries %d, n_containers %d)", who, n_entries, n_containers);
+  *total_out = 0;
+  if (n_entries == 0) return LSLAM_OK;
+  if (!begin_world || !out_poses) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: begin_world and out_poses are required", who);
+  if (n_containers > 0 && !n_points) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: n_points is required", who);
+  if (!entry_container && n_containers != n_entries)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: without entry_container entry i uses container i, so n_containers (%d) must equal n_entries (%d)",
+                     who, n_containers, n_entries);
+  if ((int)map->levels.size() > kGnMaxLevels) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d pyramid levels", kGnMaxLevels);
+  size_t total = 0;
+  for (int k = 0; k < n_containers; k++) {
+    const int n = n_points[k];
+    if (n < 0) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: container %d has a negative point count (%d)", who, k, n);
+    if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per scan are supported (got %d)", kMaxBeams, n);
+    if (map->ordered_sums && (size_t)n * 9 * sizeof(float) > 150 * 1024)
+      return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per scan in matchData", (int)(150 * 1024 / 36));
+    total += (size_t)n;
+  }
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "batch too large");
+  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: points_xy is required", who);
+  if (entry_container)
+    for (int e = 0; e < n_entries; e++)
+      if (entry_container[e] < 0 || entry_container[e] >= n_containers)
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: entry %d names container %d of %d", who, e, entry_container[e], n_containers);
+  *total_out = total;
+  return LSLAM_OK;
+}
+
+int match_batch_launch(lslam_map* map, int n_entries, int n_containers, const float* d_pts, const int32_t* n_points,
+                       const int32_t* entry_container, const float* d_begin, float* d_pose, float* d_cov) {
+  lslam_context* ctx = map->ctx;
+  {
+    int rc = flush_pending(map);  // the matcher reads the float planes
+    if (rc) return rc;
+  }
+  std::vector<int> first((size_t)n_containers + 1, 0);
+  int n_max = 0;
+  for (int k = 0; k < n_containers; k++) {
+    first[k + 1] = first[k] + n_points[k];
+    n_max = std::max(n_max, n_points[k]);
+  }
+  std::vector<int2> ent((size_t)n_entries);
+  for (int e = 0; e < n_entries; e++) {
+    const int k = entry_container ? entry_container[e] : e;
+    ent[e] = make_int2(first[k], n_points[k]);
+  }
+  LSLAM_HIP(ctx, map->d_gnb_ent.reserve((size_t)n_entries));
+  // (pageable source: the runtime has staged it when the call returns, like the batched update's scan headers)
+  LSLAM_HIP(ctx, hipMemcpyAsync(map->d_gnb_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+  GnLevels lv;
+  lv.n_levels = (int)map->levels.size();
+  for (int i = 0; i < lv.n_levels; i++) {
+    const Level& L = map->levels[i];
+    lv.sx[i] = L.sx; lv.sy[i] = L.sy; lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
+    lv.logodds[i] = L.d_logodds;
+  }
+  const int2* d_ent = map->d_gnb_ent.p;
+  if (map->ordered_sums) {
+    const size_t lds = (size_t)std::max(n_max, 1) * 9 * sizeof(float);
+    if (lds > 64 * 1024)
+      LSLAM_HIP(ctx, hipFuncSetAttribute((const void*)k_gn_match_batch_ordered, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    launch(ctx, "gn_match_batch", k_gn_match_batch_ordered, dim3((unsigned)n_entries), dim3(n_max > 512 ? 1024 : 256), lds, lv,
+           d_pts, d_ent, d_begin, d_pose, d_cov);
+  } else {
+    launch(ctx, "gn_match_batch", k_gn_match_batch, dim3((unsigned)((n_entries + kGnBatchWaves - 1) / kGnBatchWaves)),
+           dim3(64 * kGnBatchWaves), 0, lv, d_pts, d_ent, d_begin, n_entries, d_pose, d_cov);
+  }
+  LSLAM_HIP(ctx, hipGetLastError());
+  return LSLAM_OK;
+}
+}  // namespace
+
+int lslam_map_match_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev, const int32_t* n_points,
+                              const int32_t* entry_container, const float* begin_world_dev, float* out_poses_dev,
+                              float* out_covs_dev) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  size_t total = 0;
+  int rc = match_batch_check(map, "lslam_map_match_batch_dev", n_entries, n_containers, points_xy_dev, n_points, entry_container,
+                             begin_world_dev, out_poses_dev, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(map->ctx, hipSetDevice(map->ctx->device));
+  return match_batch_launch(map, n_entries, n_containers, points_xy_dev, n_points, entry_container, begin_world_dev, out_poses_dev,
+                            out_covs_dev);
+}
+
+int lslam_map_match_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                          const int32_t* entry_container, const float* begin_world, float* out_poses, float* out_covs) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  size_t total = 0;
+  int rc = match_batch_check(map, "lslam_map_match_batch", n_entries, n_containers, points_xy, n_points, entry_container, begin_world,
+                             out_poses, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  rc = stage_points(map, points_xy, (int)total);  // -> d_pts (a staging buffer of the updates; not the cached container)
+  if (rc) return rc;
+  const size_t B = (size_t)n_entries;
+  LSLAM_HIP(ctx, map->d_gnb_io.reserve(15 * B));
+  float* d_begin = map->d_gnb_io.p;
+  float* d_pose = d_begin + 3 * B;
+  float* d_cov = d_pose + 3 * B;
+  LSLAM_HIP(ctx, hipMemcpyAsync(d_begin, begin_world, 3 * B * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  rc = match_batch_launch(map, n_entries, n_containers, map->d_pts.p, n_points, entry_container, d_begin, d_pose,
+                          out_covs ? d_cov : (float*)nullptr);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipMemcpyAsync(out_poses, d_pose, 3 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_covs) LSLAM_HIP(ctx, hipMemcpyAsync(out_covs, d_cov, 9 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // one wait for the whole batch
+  return LSLAM_OK;
 }
 
 int lslam_map_set_option(lslam_map* map, int option, int value) {

@@ -333,6 +333,16 @@ class MapRepGpu {
     int rc = lslam_map_match_data(h_, pointsXY, n, origo, beginEstimateWorld, outPose, outCov);
     if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
   }
+  // Many matchData calls against the map as it is, in one launch: entry e = (container entryContainer[e], start pose
+  // beginEstimatesWorld[e]); entryContainer == nullptr: entry i uses container i.  pointsXY: the containers back to back,
+  // nPoints[nContainers].  A pure query: NO container is cached (the next updateByScan still feeds the levels above 0
+  // from the last matchData's).  outCovs may be nullptr.
+  void matchDataBatch(int nEntries, const float* beginEstimatesWorld, int nContainers, const float* pointsXY,
+                      const int32_t* nPoints, const int32_t* entryContainer, float* outPoses, float* outCovs) {
+    int rc = lslam_map_match_batch(h_, nEntries, nContainers, pointsXY, nPoints, entryContainer, beginEstimatesWorld, outPoses,
+                                   outCovs);
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
   // getGridMap(level) contents: log-odds plane / the int8 data of nav_msgs::OccupancyGrid
   void readLogOdds(int level, float* out) { lslam_map_read_logodds(h_, level, out); }
   void readOccupancy(int level, int8_t* out) { lslam_map_read_occupancy_i8(h_, level, out); }

@@ -579,6 +579,29 @@ int lslam_map_update_just_once(lslam_map* map, const float* points_xy, int n,
  * (the last Hessian, ScanMatcher.h:82-86).  n = 0 returns begin_world unchanged (ScanMatcher.h:96). */
 int lslam_map_match_data(lslam_map* map, const float* points_xy, int n, const float origo_xy[2],
                          const float begin_world[3], float out_pose[3], float out_cov[9]);
+/* BATCHED matchData: n_entries matches against the map as it is, in ONE launch and with one wait for all of them.  Entry e
+ * returns exactly what lslam_map_match_data returns for (container entry_container[e], begin_world[e]): coarse to fine over
+ * all levels, 3+1 / 5+1 iterations, the +-0.2 heading step clamp, normalize_angle, the last Hessian as covariance.  For
+ * callers with many matches against the same pyramid: one scan from K candidate start poses (re-localisation), a particle
+ * front-end, a log replayed against a finished map, a recorded trajectory being scored.
+ * points_xy: the n_containers containers back to back (sum of n_points[] points, level-0 map-cell units, as for
+ * lslam_map_update_batch); n_points[n_containers]; entry_container[n_entries] names each entry's container -- one container
+ * may serve any number of entries (K hypotheses of one scan upload it once) --, or NULL: entry i uses container i (then
+ * n_containers == n_entries); begin_world[n_entries][3]; out_poses[n_entries][3]; out_covs[n_entries][9], may be NULL.
+ * An entry whose container is empty returns its begin_world bit for bit; n_entries == 0 is LSLAM_OK and launches nothing.
+ * A PURE QUERY: unlike lslam_map_match_data it does not replace the cached container the next updateByScan feeds to the
+ * levels above 0 (lslam_map_cached_points is unchanged) and it changes no plane; like every reader it enqueues a pending
+ * pipelined apply first.  An entry's result depends on its container, its start pose and the map only, not on the batch
+ * around it.  LSLAM_MAP_OPT_ORDERED_SUMS = 1: one block per entry of the ordered kernel, bit-identical to the single
+ * ordered call (and bound by its 4266 points per container).
+ * The host form returns with the results in the caller's arrays.  The _dev form takes points_xy, begin_world, out_poses and
+ * out_covs in HBM (n_points / entry_container stay host arrays and have been copied when it returns) and is ASYNCHRONOUS
+ * on lslam_stream(): the results are valid after lslam_synchronize or the caller's own event. */
+int lslam_map_match_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                          const int32_t* entry_container, const float* begin_world, float* out_poses, float* out_covs);
+int lslam_map_match_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev,
+                              const int32_t* n_points, const int32_t* entry_container, const float* begin_world_dev,
+                              float* out_poses_dev, float* out_covs_dev);
 /* matchData adds its nine Hessian / gradient sums over the points in PARALLEL (tree sums in fp32, float32 exp / sin / cos):
  * within 1e-5 of the reference's poses on the test sequences, tolerance 1e-4 m / 1e-4 rad.  LSLAM_MAP_OPT_ORDERED_SUMS = 1
  * selects the kernel that adds them in point order like the reference's sequential loop (H/matcher/ScanMatcher.h:94-126)
@@ -638,7 +661,7 @@ int lslam_map_read_occupancy_i8(lslam_map* map, int level, int8_t* out_host);
 void* lslam_map_cells_dev_ptr(lslam_map* map, int level); /* float log-odds plane in HBM (flushes, see below) */
 /* lslam_map_update_by_scan[_dev] / _by_container are PIPELINED: a call launches [apply of the previous scan | mark of
  * this scan] as ONE kernel and leaves this scan's apply pending (one launch per scan in steady state instead of two
- * dependent ones; bit-identical planes).  Every reader in this library -- lslam_map_read_*, lslam_map_match_*, the batched
+ * dependent ones; bit-identical planes).  Every reader in this library -- lslam_map_read_*, lslam_map_match_* (lslam_map_match_batch* included), the batched
  * update, lslam_map_cells_dev_ptr, lslam_synchronize -- enqueues the pending apply first.  A caller that consumes the raw
  * plane from its OWN stream calls lslam_map_flush before recording its event on lslam_stream(). */
 int lslam_map_flush(lslam_map* map);
