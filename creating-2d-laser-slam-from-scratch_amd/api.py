@@ -329,6 +329,16 @@ def lib() -> C.CDLL:
     L.lslam_map_update_by_container.argtypes = [vp, vp]
     L.lslam_map_update_batch.argtypes = [vp, i32, vp, vp, vp, vp]
     L.lslam_map_update_batch_dev.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.lslam_hector_create.argtypes = [vp, C.POINTER(vp)]
+    L.lslam_hector_destroy.argtypes = [vp]
+    L.lslam_hector_destroy.restype = None
+    L.lslam_hector_reset.argtypes = [vp]
+    L.lslam_hector_set_update_thresholds.argtypes = [vp, C.c_float, C.c_float]
+    L.lslam_hector_set_option.argtypes = [vp, i32, i32]
+    L.lslam_hector_process_many.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp]
+    L.lslam_hector_process_many_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_state.argtypes = [vp, vp, vp, vp]
+    L.lslam_hector_stats.argtypes = [vp, vp]
     L.lslam_pool_create.argtypes = [i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_create_on.argtypes = [vp, i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_destroy.argtypes = [vp]
@@ -1135,6 +1145,8 @@ class OccGridMap:
 
     def close(self):
         if getattr(self, "h", None):
+            for proc in list(getattr(self, "_processors", ())):  # a HectorProcessor borrows its map
+                proc.close()
             self.L.lslam_map_destroy(self.h)
             self.h = None
 
@@ -1305,6 +1317,108 @@ class OccGridMap:
 
     def cells_dev_ptr(self, level: int = 0) -> int:
         return self.L.lslam_map_cells_dev_ptr(self.h, level)
+
+
+HECTOR_RECORD = np.dtype([("pose", np.float32, 3), ("cov", np.float32, (3, 3)), ("updated", np.int32), ("n_points", np.int32),
+                          ("pad", np.int32, 2)])
+assert HECTOR_RECORD.itemsize == 64
+
+
+class HectorProcessor:
+    """hectorslam::HectorSlamProcessor (H/slam_main/HectorSlamProcessor.h:57-117) streamed on the device: many scans per
+    call, the pose chain, the map-update decision and the update geometry never leave the GPU; one host synchronisation
+    per call.  Borrows `map` (an OccGridMap), which stays usable through its own methods between calls."""
+
+    def __init__(self, map: "OccGridMap"):
+        self.map, self.ctx, self.L = map, map.ctx, map.L
+        h = C.c_void_p()
+        self.ctx.check(self.L.lslam_hector_create(map.h, C.byref(h)))
+        self.h = h
+        if not hasattr(map, "_processors"):
+            map._processors = []
+        map._processors.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_hector_destroy(self.h)
+            self.h = None
+            if self in getattr(self.map, "_processors", ()):
+                self.map._processors.remove(self)
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx.check(self.L.lslam_hector_reset(self.h))
+
+    def set_update_thresholds(self, min_dist: float, min_angle: float):
+        self.ctx.check(self.L.lslam_hector_set_update_thresholds(self.h, min_dist, min_angle))
+
+    def set_option(self, name: str, value: int):
+        """'fabs_angle_gate': compare fabsf of the wrapped heading difference instead of the reference toolchain's abs(int)."""
+        self.ctx.check(self.L.lslam_hector_set_option(self.h, {"fabs_angle_gate": 1}[name], int(value)))
+
+    @staticmethod
+    def _hints_flags(n, pose_hints, map_without_matching):
+        hints = None if pose_hints is None else np.ascontiguousarray(pose_hints, dtype=np.float32).reshape(n, 3)
+        if map_without_matching is None:
+            flags = None
+        else:
+            flags = np.ascontiguousarray(np.broadcast_to(np.asarray(map_without_matching, dtype=np.uint8), (n,)))
+        return hints, flags
+
+    def process_many(self, ranges, scan: HectorScan, pose_hints=None, map_without_matching=None) -> np.ndarray:
+        """ranges: [n_scans, n_readings] float32 LaserScans -> HECTOR_RECORD[n_scans].  pose_hints None: chained."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        r = r.reshape(-1, r.shape[-1]) if r.ndim != 2 else r
+        n = r.shape[0]
+        hints, flags = self._hints_flags(n, pose_hints, map_without_matching)
+        out = np.zeros(n, HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many(
+            self.h, C.byref(scan), n, r.shape[1], r.ctypes.data, r.shape[1], None if hints is None else hints.ctypes.data,
+            None if flags is None else flags.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_points(self, containers, pose_hints=None, map_without_matching=None, origos_xy=None, counts=None) -> np.ndarray:
+        """containers: a list of (n, 2) float32 arrays in level-0 cell units, or -- with `counts` -- one packed array."""
+        if counts is None:
+            counts = np.array([len(p) for p in containers], dtype=np.int32)
+            pts = (np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in containers])
+                   if len(containers) else np.zeros((0, 2), np.float32))
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            pts = np.asarray(containers, dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        n = len(counts)
+        hints, flags = self._hints_flags(n, pose_hints, map_without_matching)
+        o = None if origos_xy is None else np.ascontiguousarray(np.broadcast_to(np.asarray(origos_xy, dtype=np.float32), (n, 2)))
+        out = np.zeros(n, HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many_points(
+            self.h, n, pts.ctypes.data, counts.ctypes.data, None if o is None else o.ctypes.data,
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data, out.ctypes.data))
+        return out
+
+    def process(self, points_xy, pose_hint=None, map_without_matching=False, origo_xy=(0.0, 0.0)):
+        """HectorSlamProcessor::update for one container (a call of one) -> its record."""
+        rec = self.process_many_points([points_xy], None if pose_hint is None else [pose_hint], [map_without_matching],
+                                       [origo_xy])
+        return rec[0]
+
+    def state(self):
+        """-> (lastScanMatchPose[3], lastScanMatchCov[3,3], lastMapUpdatePose[3])"""
+        pose, cov, upd = np.zeros(3, np.float32), np.zeros(9, np.float32), np.zeros(3, np.float32)
+        self.ctx.check(self.L.lslam_hector_state(self.h, pose.ctypes.data, cov.ctypes.data, upd.ctypes.data))
+        return pose, cov.reshape(3, 3), upd
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_hector_stats(self.h, out))
+        return dict(zip(("scans", "map_updates", "calls", "host_syncs"), (int(v) for v in out)))
 
 
 class GMappingMap:

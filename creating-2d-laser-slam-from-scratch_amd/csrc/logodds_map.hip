@@ -22,7 +22,9 @@
 // cells; nothing here is GEMM-shaped.
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <vector>
 
@@ -1276,6 +1278,413 @@ k_gn_match_batch_ordered(GnLevels lv, const float* __restrict__ pts, const int2*
 }
 
 
+// ------------------------------------------------------------------------------------------
+// STREAMED HectorSlamProcessor (lslam_hector_*): HectorSlamProcessor::update (H/slam_main/HectorSlamProcessor.h:81-108) for a
+// recorded stretch of scans with the pose chain, the update decision and the update geometry kept on the device.  The
+// host-driven loop pays three blocking round trips per scan (the projected count, the matched pose, then cosf / sinf /
+// getMapCoordsPose / the begin cell of every level computed from that pose before the update can be enqueued); here a scan
+// is [k_hector_project] -> k_hs_match_* -> k_hs_mark -> k_hs_apply on the context's one stream and the host waits once
+// per call.  No hand-over words, no spinning kernel, no cooperative launch: stream order is the only ordering.
+//   HsState        the processor's three state vectors and covariance, the live and the cached container's counts, the
+//                  cached origo, this scan's decision and -- per level -- what update_impl fills into LevelGeom on the host
+//   k_hs_match_*   k_gn_match_reg's / k_gn_match_fast's statements (hs_match_*_body, a copy) on a count and a start pose read from the device (same bits as
+//                  lslam_map_match_data for the same container, start pose, map and LSLAM_GN_THREADS); its last phase, one
+//                  thread, is the gate (H/util/UtilFunctions.h:72-91) and the geometry of every level
+//   k_hs_mark / k_hs_apply   logodds_mark_wave / logodds_apply_wave (the two-kernel, non-deferred update) with geometry,
+//                  point pointer and count read from HsState; all levels in one launch each (blockIdx.y = level), the grid
+//                  sized for the capacity; a block returns at once when the scan does not update or its beams lie beyond
+//                  the count
+// Trigonometry of the geometry: the reference evaluates Eigen::Rotation2Df with the host libm.  A scan taken without
+// matching has the host's hint as its pose, so the host sends cosf / sinf of it (bit for bit update_impl); a matched pose
+// exists on the device only and gets (float)cos((double)theta), (float)sin((double)theta).
+// ------------------------------------------------------------------------------------------
+struct HsLevelGeom {
+  float c, s, tx, ty;
+  float ox, oy, factor;
+  int bx, by;
+  uint32_t epoch;
+};
+struct HsState {
+  // ---- kHsPersistWords words that outlive a call (the host mirrors them: up at the start of a call, down at its end)
+  float match_pose[3];    // lastScanMatchPose
+  float cov[9];           // lastScanMatchCov
+  float update_pose[3];   // lastMapUpdatePose
+  int n_live;             // points of the live container (k_hector_project's count, or the caller's)
+  int n_cached;           // MapRepMultiMap::dataContainers: size and origo of what the last matchData cached
+  float cached_origo[2];
+  int updated;            // this scan's decision
+  // ---- per scan
+  HsLevelGeom lv[kGnMaxLevels];
+};
+constexpr int kHsPersistWords = 20;
+static_assert(offsetof(HsState, lv) == kHsPersistWords * 4, "HsState: the persistent words come first");
+
+struct HsScan {           // what the host knows of one scan (kernel argument)
+  float hint[3];          // poseHintWorld; unused when chain
+  float hint_c, hint_s;   // host cosf / sinf of hint[2] (host_trig)
+  int chain;              // start from HsState::match_pose (hector_slam.cc:200-204)
+  int no_match;           // map_without_matching
+  int host_trig;
+  float origo[2];         // the live container's origo
+  float min_dist, min_angle;
+  int fabs_gate;
+  int capacity;           // points the buffers behind `pts` / the cache hold per scan
+  uint32_t epoch[kGnMaxLevels];
+};
+
+// util::poseDifferenceLargerThan (H/util/UtilFunctions.h:72-91) in fp32: norm() = sqrt(dx*dx + dy*dy); the heading
+// difference wrapped once by +-2 pi in double (M_PI * 2.0f is a double product); then -- the form the reference's toolchain
+// compiles -- the unqualified abs(int): the difference truncated toward zero.  fabs_gate: fabsf instead.
+__device__ __forceinline__ bool hs_pose_difference_larger_than(const float* p, const float* q, float min_dist, float min_angle,
+                                                               int fabs_gate) {
+  const float dx = p[0] - q[0], dy = p[1] - q[1];
+  if (sqrtf(dx * dx + dy * dy) > min_dist) return true;
+  float ad = p[2] - q[2];
+  const double pi = 3.14159265358979323846;
+  if ((double)ad > pi) ad = (float)((double)ad - pi * 2.0);
+  else if ((double)ad < -pi) ad = (float)((double)ad + pi * 2.0);
+  if (fabs_gate) return fabsf(ad) > min_angle;
+  return (float)abs((int)ad) > min_angle;
+}
+
+// The matcher of the streamed kernels: the statements of k_gn_match_fast / k_gn_match_reg, DUPLICATED as device functions
+// that hand pose[3] and H[9] back in every thread (the existing kernels stay exactly as they were compiled; sharing one body
+// re-scheduled them).  Keep the two pairs in step: a change to the arithmetic of one belongs in the other.
+template <int NT>
+__device__ __forceinline__ void hs_match_fast_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
+                                                   int n, int pts_in_lds, float bx, float by, float bth, float* pose, float* H) {
+  extern __shared__ float s_pts[];  // [2n] when pts_in_lds
+  constexpr int NW = NT / 64;
+  __shared__ float s_part[2][NW][12];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int i = tid; i < 2 * n; i += NT) {
+    const float v = pts[i];
+    if (pts_in_lds) s_pts[i] = v;
+    if (cache_dst) cache_dst[i] = v;
+  }
+  const float* P = pts_in_lds ? s_pts : (cache_dst ? cache_dst : pts);
+  __syncthreads();  // (a thread reads points other threads staged; cache_dst is only re-read by its own writers' block)
+  float tmp0 = bx, tmp1 = by, tmp2 = bth;
+#pragma unroll
+  for (int q = 0; q < 9; q++) H[q] = 0.0f;
+  int flip = 0;
+  for (int L = lv.n_levels - 1; L >= 0; --L) {
+    if (n == 0) continue;
+    const float* lo = lv.logodds[L];
+    const int sx = lv.sx[L], sy = lv.sy[L];
+    const float sc = lv.scale[L];
+    const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
+    const int iters = 1 + (L == 0 ? 5 : 3);
+    // getMapCoordsPose (GridMapBase.h:238-242)
+    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];
+    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
+    float e2 = tmp2;
+    const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
+    for (int it = 0; it < iters; it++) {
+      float s, c;
+      sincosf(e2, &s, &c);
+      float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 2
+      for (int i = tid; i < n; i += NT) {
+        const float px = P[2 * i] * factor, py = P[2 * i + 1] * factor;
+        const float cx = (c * px + (-s) * py) + e0;
+        const float cy = (s * px + c * py) + e1;
+        float v = 0.0f, gxv = 0.0f, gyv = 0.0f;
+        if (!(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y)) {  // pointOutOfMapBounds (:60-63)
+          const int ix = (int)cx, iy = (int)cy;
+          const float fx = cx - (float)ix, fy = cy - (float)iy;
+          const int index = iy * sx + ix;
+          const float l0 = lo[index], l1 = lo[index + 1], l2 = lo[index + sx], l3 = lo[index + sx + 1];
+          const float i0 = gn_prob_f(l0), i1 = gn_prob_f(l1), i2 = gn_prob_f(l2), i3 = gn_prob_f(l3);
+          const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
+          const float xi = 1.0f - fx, yi = 1.0f - fy;
+          v = ((i0 * xi + i1 * fx) * (yi)) + ((i2 * xi + i3 * fx) * (fy));
+          gxv = -((dx1 * yi) + (dx2 * fy));
+          gyv = -((dy1 * xi) + (dy2 * fx));
+        }
+        const float funVal = 1.0f - v;
+        const float rotDeriv = ((-s * px - c * py) * gxv + (c * px - s * py) * gyv);
+        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
+        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
+        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
+      }
+#pragma unroll
+      for (int q = 0; q < 9; q++) {
+        const float t = gn_wave_sum(acc[q]);
+        if (lane == 0) s_part[flip][wv][q] = t;
+      }
+      __syncthreads();
+      // lane q < 9 of every wave adds the NW partials of sum q (NW LDS reads instead of 9 NW per lane), readlane hands
+      // the nine totals to all lanes
+      float mine = 0.0f;
+      if (lane < 9) {
+        mine = s_part[flip][0][lane];
+#pragma unroll
+        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
+      }
+      float sum[9];
+#pragma unroll
+      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
+      flip ^= 1;  // the next iteration writes the other buffer: no second barrier needed
+      gn_solve_step(sum, H, e0, e1, e2);
+    }
+    {
+      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
+      const double two_pi = 2.0f * 3.14159265358979323846;
+      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
+      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
+      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
+      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
+      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
+      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
+      tmp0 = (l00 * e0 + l01 * e1) + wt0;
+      tmp1 = (l10 * e0 + l11 * e1) + wt1;
+      tmp2 = a;
+    }
+  }
+  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
+}
+
+template <int NT, int PMAX>
+__device__ __forceinline__ void hs_match_reg_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
+                                                  int n, float bx, float by, float bth, float* pose, float* H) {
+  constexpr int NW = NT / 64;
+  __shared__ float s_part[2][NW][12];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float px0[PMAX], py0[PMAX];
+  bool have[PMAX];
+#pragma unroll
+  for (int p = 0; p < PMAX; p++) {
+    const int i = tid + p * NT;
+    have[p] = i < n;
+    float2 v = make_float2(0.0f, 0.0f);
+    if (have[p]) {
+      v = reinterpret_cast<const float2*>(pts)[i];
+      if (cache_dst) reinterpret_cast<float2*>(cache_dst)[i] = v;
+    }
+    px0[p] = v.x;
+    py0[p] = v.y;
+  }
+  float tmp0 = bx, tmp1 = by, tmp2 = bth;
+#pragma unroll
+  for (int q = 0; q < 9; q++) H[q] = 0.0f;
+  int flip = 0;
+  for (int L = lv.n_levels - 1; L >= 0; --L) {
+    if (n == 0) continue;
+    const float* __restrict__ lo = lv.logodds[L];
+    const int sx = lv.sx[L], sy = lv.sy[L];
+    const float sc = lv.scale[L];
+    const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
+    const int iters = 1 + (L == 0 ? 5 : 3);
+    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
+    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
+    float e2 = tmp2;
+    const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
+    float px[PMAX], py[PMAX];
+#pragma unroll
+    for (int p = 0; p < PMAX; p++) {
+      px[p] = px0[p] * factor;
+      py[p] = py0[p] * factor;
+    }
+    for (int it = 0; it < iters; it++) {
+      float s, c;
+      gn_sincos(e2, &s, &c);
+      int idx[PMAX];
+      float fx[PMAX], fy[PMAX];
+      bool inb[PMAX];
+#pragma unroll
+      for (int p = 0; p < PMAX; p++) {
+        const float cx = (c * px[p] + (-s) * py[p]) + e0;
+        const float cy = (s * px[p] + c * py[p]) + e1;
+        inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
+        const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;
+        fx[p] = cx - (float)ix;
+        fy[p] = cy - (float)iy;
+        idx[p] = iy * sx + ix;
+      }
+      float l0[PMAX], l1[PMAX], l2[PMAX], l3[PMAX];
+#pragma unroll
+      for (int p = 0; p < PMAX; p++) {
+        l0[p] = lo[idx[p]];
+        l1[p] = lo[idx[p] + 1];
+        l2[p] = lo[idx[p] + sx];
+        l3[p] = lo[idx[p] + sx + 1];
+      }
+      float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int p = 0; p < PMAX; p++) {
+        const float i0 = gn_prob_f(l0[p]), i1 = gn_prob_f(l1[p]), i2 = gn_prob_f(l2[p]), i3 = gn_prob_f(l3[p]);
+        const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
+        const float xi = 1.0f - fx[p], yi = 1.0f - fy[p];
+        const float v = inb[p] ? ((i0 * xi + i1 * fx[p]) * (yi)) + ((i2 * xi + i3 * fx[p]) * (fy[p])) : 0.0f;
+        const float gxv = inb[p] ? -((dx1 * yi) + (dx2 * fy[p])) : 0.0f;
+        const float gyv = inb[p] ? -((dy1 * xi) + (dy2 * fx[p])) : 0.0f;
+        const float funVal = have[p] ? 1.0f - v : 0.0f;
+        const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
+        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
+        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
+        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
+      }
+      gn_wave_sums9(acc);
+      if (lane == 63) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) s_part[flip][wv][q] = acc[q];
+      }
+      __syncthreads();
+      float mine = 0.0f;
+      if (lane < 9) {
+        mine = s_part[flip][0][lane];
+#pragma unroll
+        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
+      }
+      float sum[9];
+#pragma unroll
+      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
+      flip ^= 1;  // the next iteration writes the other buffer: one barrier per iteration
+      gn_solve_step(sum, H, e0, e1, e2);
+    }
+    {
+      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
+      const double two_pi = 2.0f * 3.14159265358979323846;
+      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
+      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
+      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
+      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
+      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
+      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
+      tmp0 = (l00 * e0 + l01 * e1) + wt0;
+      tmp1 = (l10 * e0 + l11 * e1) + wt1;
+      tmp2 = a;
+    }
+  }
+  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
+}
+
+// last phase of a streamed match, ONE thread: state, record, gate, geometry (HectorSlamProcessor.h:98-107 + update_impl)
+__device__ __forceinline__ void hs_finish(const GnLevels& lv, const HsScan& sc, HsState* st,
+                                          lslam_hector_record* __restrict__ rec, const float* pose, const float* H, int n) {
+  if (!sc.no_match) {
+    if (n > 0)  // ScanMatcher.h:96: an empty container leaves covMatrix untouched
+      for (int q = 0; q < 9; q++) st->cov[q] = H[q];
+    st->n_cached = n;  // dataContainers[..].setFrom (MapRepMultiMap.h:161), also when empty
+    st->cached_origo[0] = sc.origo[0];
+    st->cached_origo[1] = sc.origo[1];
+  }
+  st->n_live = n;
+  for (int q = 0; q < 3; q++) st->match_pose[q] = pose[q];
+  const bool upd = hs_pose_difference_larger_than(pose, st->update_pose, sc.min_dist, sc.min_angle, sc.fabs_gate) || sc.no_match;
+  st->updated = upd ? 1 : 0;
+  if (upd) {
+    for (int q = 0; q < 3; q++) st->update_pose[q] = pose[q];
+    float c, s;
+    if (sc.host_trig) { c = sc.hint_c; s = sc.hint_s; }
+    else { c = (float)cos((double)pose[2]); s = (float)sin((double)pose[2]); }
+    const float co0 = st->cached_origo[0], co1 = st->cached_origo[1];
+    for (int L = 0; L < lv.n_levels; L++) {
+      HsLevelGeom g;
+      g.factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);  // DataPointContainer::setFrom factor (MapRepMultiMap.h:161)
+      g.ox = L == 0 ? sc.origo[0] : co0 * g.factor;
+      g.oy = L == 0 ? sc.origo[1] : co1 * g.factor;
+      g.c = c; g.s = s;
+      g.tx = (lv.scale[L] * pose[0] + 0.0f * pose[1]) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
+      g.ty = (0.0f * pose[0] + lv.scale[L] * pose[1]) + lv.t_y[L];
+      const float bxf = (c * g.ox + (-s) * g.oy) + g.tx;            // OccGridMapBase.h:132
+      const float byf = (s * g.ox + c * g.oy) + g.ty;
+      g.bx = (int)(bxf + 0.5f);                                     // :135
+      g.by = (int)(byf + 0.5f);
+      g.epoch = sc.epoch[L];
+      st->lv[L] = g;
+    }
+  }
+  if (rec) {
+    for (int q = 0; q < 3; q++) rec->pose[q] = pose[q];
+    for (int q = 0; q < 9; q++) rec->cov[q] = st->cov[q];
+    rec->updated = upd ? 1 : 0;
+    rec->n_points = n;
+    rec->pad[0] = rec->pad[1] = 0;
+  }
+}
+
+// count (clamped to the capacity before any indexing) and start pose of a streamed scan, read by every thread (ranges form:
+// n_src points INTO the state block, which is therefore nowhere __restrict__ in these kernels); the barrier
+// keeps the one thread that rewrites them in hs_finish behind every reader, also on the paths that run no iteration
+__device__ __forceinline__ int hs_begin(const HsScan& sc, const int* n_src, const HsState* st, float* b) {
+  int n = *n_src;
+  n = n < 0 ? 0 : (n > sc.capacity ? sc.capacity : n);
+  for (int q = 0; q < 3; q++) b[q] = sc.chain ? st->match_pose[q] : sc.hint[q];
+  __syncthreads();
+  return n;
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_hs_match_reg(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
+               HsState* st, lslam_hector_record* __restrict__ rec) {
+  float b[3], pose[3], H[9];
+  const int n = hs_begin(sc, n_src, st, b);
+  if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
+  else hs_match_reg_body<NT, PMAX>(lv, pts, cache_dst, n, b[0], b[1], b[2], pose, H);
+  if (threadIdx.x == 0) hs_finish(lv, sc, st, rec, pose, H, n);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_hs_match_fast(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
+                int pts_in_lds, HsState* st, lslam_hector_record* __restrict__ rec) {
+  float b[3], pose[3], H[9];
+  const int n = hs_begin(sc, n_src, st, b);
+  if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
+  else hs_match_fast_body<NT>(lv, pts, cache_dst, n, pts_in_lds, b[0], b[1], b[2], pose, H);
+  if (threadIdx.x == 0) hs_finish(lv, sc, st, rec, pose, H, n);
+}
+
+struct HsLevels {  // what does not change from scan to scan
+  int n_levels;
+  int sx[kGnMaxLevels], sy[kGnMaxLevels];
+  float lo_free, lo_occ;
+  uint32_t* free_key[kGnMaxLevels];
+  uint32_t* occ_key[kGnMaxLevels];
+  float* logodds[kGnMaxLevels];
+};
+
+__device__ __forceinline__ LevelGeom hs_level_geom(const HsLevels& lv, const HsState* __restrict__ st, int L) {
+  const HsLevelGeom h = st->lv[L];
+  LevelGeom g;
+  g.sx = lv.sx[L]; g.sy = lv.sy[L];
+  g.c = h.c; g.s = h.s; g.tx = h.tx; g.ty = h.ty;
+  g.factor = h.factor;
+  g.ox = h.ox; g.oy = h.oy;
+  g.lo_free = lv.lo_free; g.lo_occ = lv.lo_occ;
+  g.epoch = h.epoch;
+  g.just_once = 0;
+  g.bx = h.bx; g.by = h.by;
+  g.metres_per_cell = 0.0;
+  return g;
+}
+
+// level 0 takes the live container, level i > 0 what the last matchData cached (MapRepMultiMap.h:174-191)
+__global__ void __launch_bounds__(256)
+k_hs_mark(HsLevels lv, const HsState* __restrict__ st, const float* __restrict__ pts_live, const float* __restrict__ pts_cached) {
+  if (!st->updated) return;
+  const int L = (int)blockIdx.y;
+  const int n = L == 0 ? st->n_live : st->n_cached;
+  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (wave >= n) return;
+  logodds_mark_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63, lv.free_key[L],
+                    lv.occ_key[L], nullptr);
+}
+
+__global__ void __launch_bounds__(256)
+k_hs_apply(HsLevels lv, const HsState* __restrict__ st, const float* __restrict__ pts_live, const float* __restrict__ pts_cached) {
+  if (!st->updated) return;
+  const int L = (int)blockIdx.y;
+  const int n = L == 0 ? st->n_live : st->n_cached;
+  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (wave >= n) return;
+  logodds_apply_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63, lv.free_key[L],
+                     lv.occ_key[L], lv.logodds[L]);
+}
+
 float prob_to_logodds(float prob) {  // H/map/GridMapLogOdds.h:151-155 (log() is the double overload)
   float odds = prob / (1.0f - prob);
   return (float)log((double)odds);
@@ -2077,29 +2486,28 @@ int lslam_map_batch_stats(lslam_map* map, int64_t out[4]) {
   return LSLAM_OK;
 }
 
-int lslam_map_set_scan(lslam_map* map, const float* ranges, int n, const lslam_hector_scan* sp, int* n_points) {
-  if (!map || n < 0 || (n > 0 && !ranges) || !sp) return LSLAM_ERR_INVALID_ARGUMENT;
+namespace {
+// laser_geometry's co_sine_map_ (rebuilt when the scan geometry changes): host libm, like the reference's stack
+int ensure_cossin(lslam_map* map, int n, const lslam_hector_scan* sp, bool* rebuilt = nullptr) {
   lslam_context* ctx = map->ctx;
-  if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d readings per scan (got %d)", kMaxBeams, n);
-  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n, 1) + 4));
-  LSLAM_HIP(ctx, map->d_scan_ranges.reserve((size_t)std::max(n, 1)));
-  if (n > map->cs_n || sp->angle_min != map->cs_angle_min || sp->angle_increment != map->cs_angle_inc) {
-    // laser_geometry's co_sine_map_ (rebuilt when the scan geometry changes): host libm, like the reference's stack
-    std::vector<double2> cs((size_t)std::max(n, 1));
-    for (int i = 0; i < n; i++) {
-      const double a = (double)sp->angle_min + (double)i * (double)sp->angle_increment;
-      cs[i] = make_double2(cos(a), sin(a));
-    }
-    LSLAM_HIP(ctx, map->d_cossin.reserve(cs.size()));
-    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_cossin.p, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
-    LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // cs dies with this scope
-    map->cs_n = n;
-    map->cs_angle_min = sp->angle_min;
-    map->cs_angle_inc = sp->angle_increment;
+  if (rebuilt) *rebuilt = false;
+  if (!(n > map->cs_n || sp->angle_min != map->cs_angle_min || sp->angle_increment != map->cs_angle_inc)) return LSLAM_OK;
+  std::vector<double2> cs((size_t)std::max(n, 1));
+  for (int i = 0; i < n; i++) {
+    const double a = (double)sp->angle_min + (double)i * (double)sp->angle_increment;
+    cs[i] = make_double2(cos(a), sin(a));
   }
-  if (n > 0)
-    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_scan_ranges.p, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  LSLAM_HIP(ctx, map->d_cossin.reserve(cs.size()));
+  LSLAM_HIP(ctx, hipMemcpyAsync(map->d_cossin.p, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // cs dies with this scope
+  map->cs_n = n;
+  map->cs_angle_min = sp->angle_min;
+  map->cs_angle_inc = sp->angle_increment;
+  if (rebuilt) *rebuilt = true;
+  return LSLAM_OK;
+}
+
+ProjectCfg project_cfg(const lslam_map* map, int n, const lslam_hector_scan* sp) {
   ProjectCfg c;
   c.n = n;
   c.range_min = sp->range_min;
@@ -2113,6 +2521,24 @@ int lslam_map_set_scan(lslam_map* map, const float* ranges, int n, const lslam_h
   c.sy = sin((double)sp->laser_yaw);
   c.tx = sp->laser_x; c.ty = sp->laser_y; c.tz = sp->laser_z;
   c.scale_to_map = map->levels[0].scale_to_map;
+  return c;
+}
+}  // namespace
+
+int lslam_map_set_scan(lslam_map* map, const float* ranges, int n, const lslam_hector_scan* sp, int* n_points) {
+  if (!map || n < 0 || (n > 0 && !ranges) || !sp) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d readings per scan (got %d)", kMaxBeams, n);
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n, 1) + 4));
+  LSLAM_HIP(ctx, map->d_scan_ranges.reserve((size_t)std::max(n, 1)));
+  {
+    int rc = ensure_cossin(map, n, sp);
+    if (rc) return rc;
+  }
+  if (n > 0)
+    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_scan_ranges.p, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  const ProjectCfg c = project_cfg(map, n, sp);
   int* d_n = reinterpret_cast<int*>(map->d_scan.p + (size_t)2 * std::max(n, 1));
   launch(ctx, "hector_project", k_hector_project, dim3(1), dim3(1024), 0, c, (const float*)map->d_scan_ranges.p,
          (const double2*)map->d_cossin.p, map->d_scan.p, d_n);
@@ -2477,6 +2903,373 @@ int lslam_map_flush(lslam_map* map) {
   lslam_context* ctx = map->ctx;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
   return flush_pending(map);
+}
+
+}  // extern "C"
+
+
+// ------------------------------------------------------------------------------------------
+// lslam_hector_*: the streamed HectorSlamProcessor (device side: k_hs_* above)
+// ------------------------------------------------------------------------------------------
+struct lslam_hector {
+  lslam_map* map = nullptr;
+  float min_dist = 0.4f, min_angle = 0.13f;  // HectorSlamProcessor.h:66-67
+  int fabs_gate = 0;
+  HsState* d_state = nullptr;
+  // host mirror of HsState's persistent words, and their pinned way up and down (one copy each per call)
+  HsState mirror;
+  uint32_t* h_io = nullptr;  // [2][kHsPersistWords]
+  lslam_hector_record* h_rec = nullptr;
+  size_t h_rec_cap = 0;
+  float* h_ranges = nullptr;  // pinned way up of a call's ranges, or of its points and counts
+  size_t h_ranges_cap = 0;
+  DevBuf<lslam_hector_record> d_rec;
+  DevBuf<float> d_ranges;
+  DevBuf<int> d_counts;
+  int64_t n_scans = 0, n_updates = 0, n_calls = 0, n_syncs = 0;
+};
+
+namespace {
+
+// HectorSlamProcessor::reset (:111-117): lastMapUpdatePose and lastScanMatchPose; lastScanMatchCov stays what it was
+void hs_reset_state(lslam_hector* h) {
+  for (int q = 0; q < 3; q++) {
+    h->mirror.update_pose[q] = FLT_MAX;
+    h->mirror.match_pose[q] = 0.0f;
+  }
+}
+
+template <typename T>
+int hs_pinned_reserve(lslam_context* ctx, T** p, size_t* cap, size_t want) {
+  if (want <= *cap) return LSLAM_OK;
+  if (*p) (void)hipHostFree(*p);  // (every call ends with a synchronise: nothing in flight reads it)
+  *p = nullptr;
+  *cap = 0;
+  const size_t n = want + want / 4 + 16;
+  LSLAM_HIP(ctx, hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault));
+  *cap = n;
+  return LSLAM_OK;
+}
+
+// what both forms refuse before anything touches the device
+int hs_check(lslam_hector* h, const char* who, int capacity) {
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  if (map->ordered_sums)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: the streamed processor runs the parallel-sum matcher; LSLAM_MAP_OPT_ORDERED_SUMS "
+                     "maps go through lslam_map_match_data / lslam_map_update_by_scan", who);
+  if ((int)map->levels.size() > kGnMaxLevels) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d pyramid levels", who, kGnMaxLevels);
+  if (capacity > kMaxBeams || map->n_cached > kMaxBeams)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d points per scan are supported (got %d)", who, kMaxBeams,
+                     std::max(capacity, map->n_cached));
+  return LSLAM_OK;
+}
+
+struct HsCall {
+  int n_scans = 0, capacity = 0;
+  const lslam_hector_scan* scan = nullptr;   // ranges form: project scan k's readings into the map's resident container
+  int n_readings = 0;
+  const float* d_points = nullptr;           // container form: the packed points in HBM,
+  const int32_t* n_points = nullptr;         //   their host counts (offsets) and
+  const float* origos = nullptr;             //   origos (may be null)
+  const float* hints = nullptr;
+  const uint8_t* no_match = nullptr;
+  lslam_hector_record* out = nullptr;
+};
+
+int hs_run(lslam_hector* h, const HsCall& c) {
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  const int n_levels = (int)map->levels.size();
+  {
+    int rc = flush_pending(map);  // the matcher reads the float planes; the streamed update is not deferred
+    if (rc) return rc;
+  }
+  // the cached container must survive a growth of its buffer (levels above 0 of a scan taken without matching read it)
+  const int cache_cap = std::max(std::max(c.capacity, map->n_cached), 1);
+  {
+    const float* old = map->d_cached.p;
+    LSLAM_HIP(ctx, map->d_cached.reserve((size_t)2 * cache_cap));
+    if (old && old != map->d_cached.p && map->n_cached > 0)
+      LSLAM_HIP(ctx, hipMemcpyAsync(map->d_cached.p, old, (size_t)2 * map->n_cached * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  LSLAM_HIP(ctx, h->d_rec.reserve((size_t)c.n_scans));
+  {
+    int rc = hs_pinned_reserve(ctx, &h->h_rec, &h->h_rec_cap, (size_t)c.n_scans);
+    if (rc) return rc;
+  }
+  // ---- state up: the processor's vectors from the mirror, the cached container's count and origo from the map (a
+  // host-driven matchData between two calls may have replaced it)
+  h->mirror.n_cached = map->n_cached;
+  h->mirror.cached_origo[0] = map->cached_origo[0];
+  h->mirror.cached_origo[1] = map->cached_origo[1];
+  h->mirror.updated = 0;
+  memcpy(h->h_io, &h->mirror, kHsPersistWords * 4);
+  LSLAM_HIP(ctx, hipMemcpyAsync(h->d_state, h->h_io, kHsPersistWords * 4, hipMemcpyHostToDevice, ctx->stream));
+  GnLevels lv;
+  HsLevels ul;
+  lv.n_levels = ul.n_levels = n_levels;
+  ul.lo_free = map->lo_free;
+  ul.lo_occ = map->lo_occ;
+  for (int i = 0; i < n_levels; i++) {
+    const Level& L = map->levels[i];
+    lv.sx[i] = ul.sx[i] = L.sx; lv.sy[i] = ul.sy[i] = L.sy;
+    lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
+    lv.logodds[i] = L.d_logodds;
+    ul.free_key[i] = L.d_free; ul.occ_key[i] = L.d_occ; ul.logodds[i] = L.d_logodds;
+  }
+  int* const d_n_live = &h->d_state->n_live;
+  ProjectCfg pc{};
+  float scan_origo[2] = {0.f, 0.f};
+  std::vector<size_t> first;
+  if (c.scan) {
+    pc = project_cfg(map, c.n_readings, c.scan);
+    // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:331)
+    scan_origo[0] = (float)(double)c.scan->laser_x * pc.scale_to_map;
+    scan_origo[1] = (float)(double)c.scan->laser_y * pc.scale_to_map;
+  } else {
+    first.assign((size_t)c.n_scans + 1, 0);
+    for (int k = 0; k < c.n_scans; k++) first[k + 1] = first[k] + (size_t)c.n_points[k];
+  }
+  // the matcher's form from the CAPACITY (the live count is the device's): as match_data_impl chooses from n
+  const int nt = map->gn_threads >= 1024 ? 1024 : (map->gn_threads >= 512 ? 512 : 256);
+  const bool reg = c.capacity <= (nt == 1024 ? 1024 * 2 : (nt == 512 ? 512 * 3 : 256 * 5));
+  const int in_lds = (size_t)2 * c.capacity * sizeof(float) <= 56 * 1024;
+  const size_t lds = !reg && in_lds ? (size_t)2 * std::max(c.capacity, 1) * sizeof(float) : 0;
+  const dim3 ugrid((unsigned)((cache_cap + 3) / 4), (unsigned)n_levels), ublock(256);
+  for (int k = 0; k < c.n_scans; k++) {
+    HsScan sc{};
+    sc.chain = c.hints ? 0 : 1;
+    sc.no_match = c.no_match && c.no_match[k] ? 1 : 0;
+    if (c.hints) {
+      for (int q = 0; q < 3; q++) sc.hint[q] = c.hints[3 * k + q];
+      sc.hint_c = cosf(sc.hint[2]);  // host libm, exactly what the reference's Eigen::Rotation2Df evaluates
+      sc.hint_s = sinf(sc.hint[2]);
+      sc.host_trig = sc.no_match;
+    }
+    sc.min_dist = h->min_dist; sc.min_angle = h->min_angle; sc.fabs_gate = h->fabs_gate;
+    sc.capacity = c.capacity;
+    // an epoch per scan and level whether or not the device updates (an unused epoch is harmless)
+    for (int li = 0; li < n_levels; li++) {
+      Level& L = map->levels[li];
+      if (L.epoch >= kMaxEpoch) {
+        int rc = clear_marks(map, L);  // stream-ordered; nothing is pending
+        if (rc) return rc;
+      }
+      sc.epoch[li] = ++L.epoch;
+    }
+    const float* pts;
+    const int* n_src;
+    if (c.scan) {
+      launch(ctx, "hs_project", k_hector_project, dim3(1), dim3(1024), 0, pc, (const float*)(h->d_ranges.p + (size_t)k * c.n_readings),
+             (const double2*)map->d_cossin.p, map->d_scan.p, d_n_live);
+      pts = map->d_scan.p;
+      n_src = d_n_live;
+      sc.origo[0] = scan_origo[0]; sc.origo[1] = scan_origo[1];
+    } else {
+      pts = c.d_points + 2 * first[k];
+      n_src = h->d_counts.p + k;
+      sc.origo[0] = c.origos ? c.origos[2 * k] : 0.f;
+      sc.origo[1] = c.origos ? c.origos[2 * k + 1] : 0.f;
+    }
+    lslam_hector_record* rec = h->d_rec.p + k;
+#define LSLAM_HS_REG(NT, PMAX) \
+  launch(ctx, "hs_match", k_hs_match_reg<NT, PMAX>, dim3(1), dim3(NT), 0, lv, sc, pts, n_src, map->d_cached.p, h->d_state, rec)
+#define LSLAM_HS_FAST(NT) \
+  launch(ctx, "hs_match", k_hs_match_fast<NT>, dim3(1), dim3(NT), lds, lv, sc, pts, n_src, map->d_cached.p, in_lds, h->d_state, rec)
+    if (reg) {
+      if (nt == 1024) LSLAM_HS_REG(1024, 2);
+      else if (nt == 512) LSLAM_HS_REG(512, 3);
+      else LSLAM_HS_REG(256, 5);
+    } else {
+      if (nt == 1024) LSLAM_HS_FAST(1024);
+      else if (nt == 512) LSLAM_HS_FAST(512);
+      else LSLAM_HS_FAST(256);
+    }
+#undef LSLAM_HS_REG
+#undef LSLAM_HS_FAST
+    launch(ctx, "hs_mark", k_hs_mark, ugrid, ublock, 0, ul, (const HsState*)h->d_state, pts, (const float*)map->d_cached.p);
+    launch(ctx, "hs_apply", k_hs_apply, ugrid, ublock, 0, ul, (const HsState*)h->d_state, pts, (const float*)map->d_cached.p);
+  }
+  LSLAM_HIP(ctx, hipGetLastError());
+  // ---- end of the call: the records and the state down, ONE wait
+  LSLAM_HIP(ctx, hipMemcpyAsync(h->h_rec, h->d_rec.p, (size_t)c.n_scans * sizeof(lslam_hector_record), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipMemcpyAsync(h->h_io + kHsPersistWords, h->d_state, kHsPersistWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  h->n_syncs++;
+  h->n_calls++;
+  h->n_scans += c.n_scans;
+  memcpy(&h->mirror, h->h_io + kHsPersistWords, kHsPersistWords * 4);
+  for (int k = 0; k < c.n_scans; k++) h->n_updates += h->h_rec[k].updated != 0;
+  if (c.out) memcpy(c.out, h->h_rec, (size_t)c.n_scans * sizeof(lslam_hector_record));
+  // what the host side of the map must know so that every lslam_map_* call goes on working on it
+  if (n_levels > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
+    map->n_cached = h->mirror.n_cached;
+    map->cached_origo[0] = h->mirror.cached_origo[0];
+    map->cached_origo[1] = h->mirror.cached_origo[1];
+  }
+  map->gn_host_n = -1;  // d_cached was rewritten on the device
+  if (c.scan) {         // the resident container of lslam_map_set_scan is the last scan's
+    map->n_scan = h->mirror.n_live;
+    map->scan_origo[0] = scan_origo[0];
+    map->scan_origo[1] = scan_origo[1];
+  }
+  return LSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lslam_hector_create(lslam_map* map, lslam_hector** out) {
+  if (!map || !out) return LSLAM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  lslam_context* ctx = map->ctx;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  lslam_hector* h = new lslam_hector();
+  h->map = map;
+  memset(&h->mirror, 0, sizeof h->mirror);
+  hs_reset_state(h);
+  if (hipMalloc((void**)&h->d_state, sizeof(HsState)) != hipSuccess ||
+      hipHostMalloc((void**)&h->h_io, 2 * kHsPersistWords * 4, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    lslam_hector_destroy(h);
+    return ctx->fail(LSLAM_ERR_HIP, "cannot allocate the streamed processor's state block");
+  }
+  (void)hipMemsetAsync(h->d_state, 0, sizeof(HsState), ctx->stream);
+  *out = h;
+  return LSLAM_OK;
+}
+
+void lslam_hector_destroy(lslam_hector* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->map->ctx->device);
+  (void)hipStreamSynchronize(h->map->ctx->stream);
+  if (h->d_state) (void)hipFree(h->d_state);
+  if (h->h_io) (void)hipHostFree(h->h_io);
+  if (h->h_rec) (void)hipHostFree(h->h_rec);
+  if (h->h_ranges) (void)hipHostFree(h->h_ranges);
+  h->d_rec.release();
+  h->d_ranges.release();
+  h->d_counts.release();
+  delete h;
+}
+
+int lslam_hector_reset(lslam_hector* h) {
+  if (!h) return LSLAM_ERR_INVALID_ARGUMENT;
+  hs_reset_state(h);
+  return lslam_map_reset(h->map);  // mapRep->reset() (HectorSlamProcessor.h:116)
+}
+
+int lslam_hector_set_update_thresholds(lslam_hector* h, float min_dist, float min_angle) {
+  if (!h) return LSLAM_ERR_INVALID_ARGUMENT;
+  h->min_dist = min_dist;
+  h->min_angle = min_angle;
+  return LSLAM_OK;
+}
+
+int lslam_hector_set_option(lslam_hector* h, int option, int value) {
+  if (!h) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (option == LSLAM_HECTOR_OPT_FABS_ANGLE_GATE) {
+    h->fabs_gate = value != 0;
+    return LSLAM_OK;
+  }
+  return h->map->ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "unknown streamed-processor option %d", option);
+}
+
+int lslam_hector_process_many(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_readings, const float* ranges,
+                              int ranges_stride, const float* pose_hints, const uint8_t* map_without_matching,
+                              lslam_hector_record* out) {
+  if (!h || n_scans < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_scans == 0) return LSLAM_OK;
+  if (!scan || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  int rc = hs_check(h, "lslam_hector_process_many", n_readings);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_readings, 1) + 4));
+  bool rebuilt = false;
+  rc = ensure_cossin(map, n_readings, scan, &rebuilt);  // (waits for its upload when the scan geometry is new)
+  if (rc) return rc;
+  h->n_syncs += rebuilt;
+  const size_t total = (size_t)n_scans * (size_t)n_readings;
+  LSLAM_HIP(ctx, h->d_ranges.reserve(std::max(total, (size_t)1)));
+  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, std::max(total, (size_t)1));
+  if (rc) return rc;
+  if (total > 0) {
+    for (int k = 0; k < n_scans; k++)
+      memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HsCall c;
+  c.n_scans = n_scans;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.out = out;
+  return hs_run(h, c);
+}
+
+int lslam_hector_process_many_points(lslam_hector* h, int n_scans, const float* points_xy, const int32_t* n_points,
+                                     const float* origos_xy, const float* pose_hints, const uint8_t* map_without_matching,
+                                     lslam_hector_record* out) {
+  if (!h || n_scans < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_scans == 0) return LSLAM_OK;
+  if (!n_points) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  size_t total = 0;
+  int cap = 0;
+  for (int k = 0; k < n_scans; k++) {
+    if (n_points[k] < 0) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_points: scan %d has a negative point count (%d)", k, n_points[k]);
+    total += (size_t)n_points[k];
+    cap = std::max(cap, n_points[k]);
+  }
+  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_points: points_xy is required");
+  int rc = hs_check(h, "lslam_hector_process_many_points", cap);
+  if (rc) return rc;
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_process_many_points: call too large");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // points, then counts, through pinned staging of the processor's own (stage_points' ring waits for a busy slot and drains
+  // the stream when it grows; the call's end has synchronised, so this buffer is never in flight here) -> d_pts, d_counts
+  const size_t words = 2 * total + (size_t)n_scans;
+  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, words);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, map->d_pts.reserve(std::max((size_t)2 * total, (size_t)2)));
+  LSLAM_HIP(ctx, h->d_counts.reserve((size_t)n_scans));
+  if (total > 0) {
+    memcpy(h->h_ranges, points_xy, 2 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_pts.p, h->h_ranges, 2 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  memcpy(h->h_ranges + 2 * total, n_points, (size_t)n_scans * sizeof(int32_t));
+  LSLAM_HIP(ctx, hipMemcpyAsync(h->d_counts.p, h->h_ranges + 2 * total, (size_t)n_scans * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HsCall c;
+  c.n_scans = n_scans;
+  c.capacity = cap;
+  c.d_points = map->d_pts.p;
+  c.n_points = n_points;
+  c.origos = origos_xy;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.out = out;
+  return hs_run(h, c);
+}
+
+int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_match_cov[9], float last_update_pose[3]) {
+  if (!h) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (last_match_pose) memcpy(last_match_pose, h->mirror.match_pose, 3 * sizeof(float));
+  if (last_match_cov) memcpy(last_match_cov, h->mirror.cov, 9 * sizeof(float));
+  if (last_update_pose) memcpy(last_update_pose, h->mirror.update_pose, 3 * sizeof(float));
+  return LSLAM_OK;
+}
+
+int lslam_hector_stats(const lslam_hector* h, int64_t out[4]) {
+  if (!h || !out) return LSLAM_ERR_INVALID_ARGUMENT;
+  out[0] = h->n_scans; out[1] = h->n_updates; out[2] = h->n_calls; out[3] = h->n_syncs;
+  return LSLAM_OK;
 }
 
 }  // extern "C"

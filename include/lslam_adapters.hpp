@@ -353,6 +353,73 @@ class MapRepGpu {
   lslam_map* h_ = nullptr;
 };
 
+// hectorslam::HectorSlamProcessor (H/slam_main/HectorSlamProcessor.h:57-117) streamed on the GPU: the match, the update
+// decision and the update of every level stay on the device (lslam_hector_*), one host synchronisation per call.  Owns its
+// MapRepGpu like the reference's processor owns its MapRepMultiMap (:61).  Use it where a stretch of scans is at hand
+// (a recorded log, a queue that has run full); HectorMapRepGpu (integration/hector_map_rep_gpu.hpp) is for the reference's
+// own processor driving the device one call at a time.
+class HectorSlamProcessorGpu {
+ public:
+  // HectorSlamProcessor(mapResolution, mapSizeX, mapSizeY, startCoords, multi_res_size) (:57-68) + the device context
+  HectorSlamProcessorGpu(lslam_context* ctx, float mapResolution, int mapSizeX, int mapSizeY, float startX, float startY,
+                         int multi_res_size)
+      : ctx_(ctx), map_(ctx, mapResolution, mapSizeX, mapSizeY, (unsigned)multi_res_size, startX, startY) {
+    check(lslam_hector_create(map_.handle(), &h_));
+  }
+  ~HectorSlamProcessorGpu() { lslam_hector_destroy(h_); }
+  HectorSlamProcessorGpu(const HectorSlamProcessorGpu&) = delete;
+  HectorSlamProcessorGpu& operator=(const HectorSlamProcessorGpu&) = delete;
+
+  // void update(const DataContainer& dataContainer, const Eigen::Vector3f& poseHintWorld, bool map_without_matching = false)
+  // (:81) for any container with getSize() / getVecEntry(i) / getOrigo() and any pose indexable by [0..2]
+  template <typename Container, typename Pose>
+  void update(const Container& dataContainer, const Pose& poseHintWorld, bool map_without_matching = false) {
+    const int n = dataContainer.getSize();
+    pts_.resize((size_t)2 * (n > 0 ? n : 1));
+    for (int i = 0; i < n; ++i) {
+      pts_[(size_t)2 * i] = dataContainer.getVecEntry(i)[0];
+      pts_[(size_t)2 * i + 1] = dataContainer.getVecEntry(i)[1];
+    }
+    const float origo[2] = {dataContainer.getOrigo()[0], dataContainer.getOrigo()[1]};
+    const float hint[3] = {poseHintWorld[0], poseHintWorld[1], poseHintWorld[2]};
+    const int32_t count = n;
+    updateMany(1, pts_.data(), &count, origo, hint, &map_without_matching, nullptr);
+  }
+  // update() for nScans containers back to back (nPoints[nScans], origos nScans x 2 or nullptr = 0); poseHints == nullptr:
+  // every scan starts from the previous result (hector_slam.cc:200-204); records may be nullptr
+  void updateMany(int nScans, const float* pointsXY, const int32_t* nPoints, const float* origosXY, const float* poseHints,
+                  const bool* mapWithoutMatching, lslam_hector_record* records) {
+    flags_.assign((size_t)(nScans > 0 ? nScans : 0), 0);
+    for (int k = 0; k < nScans && mapWithoutMatching; ++k) flags_[(size_t)k] = mapWithoutMatching[k] ? 1 : 0;
+    check(lslam_hector_process_many_points(h_, nScans, pointsXY, nPoints, origosXY, poseHints,
+                                           mapWithoutMatching ? flags_.data() : nullptr, records));
+  }
+  void reset() { check(lslam_hector_reset(h_)); }  // :111-117
+  // getLastScanMatchPose / getLastScanMatchCovariance (:120-122)
+  void getLastScanMatchPose(float out[3]) { check(lslam_hector_state(h_, out, nullptr, nullptr)); }
+  void getLastScanMatchCovariance(float out[9]) { check(lslam_hector_state(h_, nullptr, out, nullptr)); }
+  void getLastMapUpdatePose(float out[3]) { check(lslam_hector_state(h_, nullptr, nullptr, out)); }
+  float getScaleToMap() const { return map_.getScaleToMap(); }
+  int getMapLevels() const { return map_.getMapLevels(); }
+  void setUpdateFactorFree(float f) { map_.setUpdateFactorFree(f); }
+  void setUpdateFactorOccupied(float f) { map_.setUpdateFactorOccupied(f); }
+  void setMapUpdateMinDistDiff(float d) { minDist_ = d; check(lslam_hector_set_update_thresholds(h_, minDist_, minAngle_)); }
+  void setMapUpdateMinAngleDiff(float a) { minAngle_ = a; check(lslam_hector_set_update_thresholds(h_, minDist_, minAngle_)); }
+  MapRepGpu& mapRep() { return map_; }
+  lslam_hector* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  MapRepGpu map_;
+  lslam_hector* h_ = nullptr;
+  float minDist_ = 0.4f, minAngle_ = 0.13f;
+  std::vector<float> pts_;
+  std::vector<uint8_t> flags_;
+};
+
 // gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's
 // ComputeMap (gmapping.cc:171-242).  cell() reads from a host copy of the counters, refreshed after every change.
 struct IntPoint2 {  // gmapping::IntPoint

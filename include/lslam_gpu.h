@@ -667,6 +667,72 @@ void* lslam_map_cells_dev_ptr(lslam_map* map, int level); /* float log-odds plan
 int lslam_map_flush(lslam_map* map);
 
 /* ---------------------------------------------------------------------------------------- */
+/* Streamed HectorSlamProcessor (H/slam_main/HectorSlamProcessor.h:57-117): many scans per     */
+/* call, the pose chain, the update decision and the update geometry kept on the device.       */
+/* ---------------------------------------------------------------------------------------- */
+/* Per scan (HectorSlamProcessor::update, :81-108):
+ *   newPose = map_without_matching ? hint : matchData(hint, container, lastScanMatchCov)          (:88-96)
+ *   lastScanMatchPose = newPose                                                                   (:98)
+ *   if (poseDifferenceLargerThan(newPose, lastMapUpdatePose, minDist, minAngle) || map_without_matching)
+ *     updateByScan(container, newPose) on every level; lastMapUpdatePose = newPose                (:101-107)
+ * Level 0 takes the container it is handed, level i > 0 what the last matchData cached, scaled (H/slam_main/
+ * MapRepMultiMap.h:161,174-191).  Every scan is one short chain of launches on lslam_stream() -- [projection], match (the
+ * arithmetic of lslam_map_match_data's parallel-sum kernel: the same bits for the same container, start pose, map and
+ * LSLAM_GN_THREADS, the register or LDS form chosen from the readings / points per scan of the CALL), mark, apply -- whose
+ * count, start pose, decision and per-level update geometry stay in a device state block; a call makes ONE host
+ * synchronisation, at its end, whatever n_scans is.  A scan k+1 sees the map as scan k left it.
+ * The map is BORROWED: every lslam_map_* call keeps working on it between calls (the cached container, its origo and --
+ * ranges form -- the resident container of lslam_map_set_scan are the last streamed scan's).
+ * The gate is H/util/UtilFunctions.h:72-91 in fp32: sqrt(dx*dx + dy*dy) > minDist, or the heading difference, wrapped once by
+ * +-2 pi, beyond minAngle.  The reference's unqualified abs() there resolves to abs(int) with its toolchain, so the
+ * wrapped difference is truncated toward zero before the comparison: that is the default here;
+ * LSLAM_HECTOR_OPT_FABS_ANGLE_GATE = 1 compares fabsf of it.
+ * Update geometry: for a scan taken without matching the rotation is the host's cosf / sinf of the hint (bit for bit
+ * lslam_map_update_by_scan at that pose); for a matched scan the device evaluates (float)cos((double)theta) and
+ * (float)sin((double)theta), which may differ from the host libm's float functions in the last bit. */
+typedef struct lslam_hector lslam_hector;
+typedef struct lslam_hector_record { /* 64 bytes */
+  float pose[3];     /* lastScanMatchPose after this scan (:98) */
+  float cov[9];      /* lastScanMatchCov after this scan (:91; an empty or unmatched scan leaves it as it was) */
+  int32_t updated;   /* the map was updated with this scan (:101-107) */
+  int32_t n_points;  /* size of the scan's container */
+  int32_t pad[2];
+} lslam_hector_record;
+enum { LSLAM_HECTOR_OPT_FABS_ANGLE_GATE = 1 };
+/* HectorSlamProcessor ctor (:57-68) on an existing map, which it borrows (destroy the processor first): state as after
+ * reset(), thresholds 0.4 / 0.13 (:66-67) */
+int lslam_hector_create(lslam_map* map, lslam_hector** out);
+void lslam_hector_destroy(lslam_hector* h);
+/* HectorSlamProcessor::reset (:111-117): lastMapUpdatePose = FLT_MAX, lastScanMatchPose = 0, lslam_map_reset;
+ * lastScanMatchCov stays what it was, as in the reference */
+int lslam_hector_reset(lslam_hector* h);
+/* setMapUpdateMinDistDiff / setMapUpdateMinAngleDiff (:66-67) */
+int lslam_hector_set_update_thresholds(lslam_hector* h, float min_dist, float min_angle);
+int lslam_hector_set_option(lslam_hector* h, int option, int value);
+/* update() (:81-108) for n_scans LaserScans of n_readings float32 readings each (row k at ranges + k * ranges_stride): the
+ * projection of lslam_map_set_scan on the device, its count never read back.  pose_hints: n_scans x 3, or NULL = chain: scan
+ * 0 starts from lastScanMatchPose and scan k from scan k-1's result (hector_slam.cc:200-204).  map_without_matching:
+ * n_scans flags, NULL = all 0.  out: n_scans records, may be NULL.  n_scans == 0 is LSLAM_OK and does nothing.
+ * LSLAM_ERR_UNSUPPORTED (with a message) for LSLAM_MAP_OPT_ORDERED_SUMS maps, pyramids deeper than 8 levels and more than
+ * 65536 readings per scan. */
+int lslam_hector_process_many(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_readings, const float* ranges,
+                              int ranges_stride, const float* pose_hints, const uint8_t* map_without_matching,
+                              lslam_hector_record* out);
+/* the same for DataContainers: points_xy = the containers back to back in level-0 map-cell units (as lslam_map_match_batch
+ * takes them), n_points[n_scans], origos_xy n_scans x 2 or NULL = (0, 0) */
+int lslam_hector_process_many_points(lslam_hector* h, int n_scans, const float* points_xy, const int32_t* n_points,
+                                     const float* origos_xy, const float* pose_hints, const uint8_t* map_without_matching,
+                                     lslam_hector_record* out);
+/* getLastScanMatchPose / getLastScanMatchCovariance (:120-122) and lastMapUpdatePose; any pointer may be NULL.  Host only. */
+int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_match_cov[9], float last_update_pose[3]);
+/* out = {scans processed, map updates made, calls that processed scans, waits for the stream those calls made}.  The last is
+ * counted where the library waits: once per call, at its end, plus once in a ranges-form call that meets a new scan geometry
+ * (it uploads the cos / sin table and waits for it).  Inputs go up through pinned memory, so no copy blocks on the way.  NOT
+ * counted: what the runtime does inside an allocation -- a call that has to grow a staging or device buffer (the first call, or
+ * one longer than any before it) goes through hipHostMalloc / hipHostFree / hipMalloc, which may wait for the device. */
+int lslam_hector_stats(const lslam_hector* h, int64_t out[4]);
+
+/* ---------------------------------------------------------------------------------------- */
 /* lesson5 lidar motion de-skew (LidarUndistortion::CorrectLaserScan, lesson5/src/            */
 /* lidar_undistortion.cc:339-447) -- SURVEY 8(f) #4.  Pinned (round 4) against the reference's */
 /* own source compiled in place behind ROS / tf / PCL / Eigen stand-ins (oracle/shim, which    */
