@@ -704,6 +704,77 @@ __device__ __forceinline__ float gn_cof3(const float* m, int i, int j) {
   return m[3 * i1 + j1] * m[3 * i2 + j2] - m[3 * i1 + j2] * m[3 * i2 + j1];
 }
 
+// ---- the statements every form of the matcher shares: ONE copy each, plain inlined functions on values.  The library is
+// built with -ffp-contract=off, so a result's bits follow from the order of these expressions and from nothing else.
+
+// The solve + pose update after the nine sums (estimateTransformationLogLh, ScanMatcher.h:113-133); H is the Hessian as summed
+__device__ __forceinline__ void gn_solve_step(const float* sum, float* H, float& e0, float& e1, float& e2) {
+  const float d0 = sum[0], d1 = sum[1], d2 = sum[2], h00 = sum[3], h11 = sum[4], h22 = sum[5], h01 = sum[6], h02 = sum[7],
+              h12 = sum[8];
+  H[0] = h00; H[1] = h01; H[2] = h02; H[3] = h01; H[4] = h11; H[5] = h12; H[6] = h02; H[7] = h12; H[8] = h22;
+  if (h00 != 0.0f && h11 != 0.0f) {
+    const float c0 = gn_cof3(H, 0, 0), c1 = gn_cof3(H, 1, 0), c2 = gn_cof3(H, 2, 0);
+    const float det = c0 * H[0] + (c1 * H[3] + c2 * H[6]);
+    const float invdet = 1.0f / det;
+    const float Hi[9] = {c0 * invdet, c1 * invdet, c2 * invdet,
+                         gn_cof3(H, 0, 1) * invdet, gn_cof3(H, 1, 1) * invdet, gn_cof3(H, 2, 1) * invdet,
+                         gn_cof3(H, 0, 2) * invdet, gn_cof3(H, 1, 2) * invdet, gn_cof3(H, 2, 2) * invdet};
+    float sd[3];
+    // H.inverse() * dTr: Eigen's coefficient-based product sums a 3-term row as a0 + (a1 + a2) (Core/Redux.h)
+    for (int r = 0; r < 3; r++) sd[r] = Hi[3 * r] * d0 + (Hi[3 * r + 1] * d1 + Hi[3 * r + 2] * d2);
+    if (sd[2] > 0.2f) sd[2] = 0.2f; else if (sd[2] < -0.2f) sd[2] = -0.2f;
+    e0 += sd[0]; e1 += sd[1]; e2 += sd[2];
+  }
+}
+
+// level prologue: the world estimate on a level's raster, getMapCoordsPose (GridMapBase.h:238-242)
+__device__ __forceinline__ void gn_level_begin(float sc, float t_x, float t_y, float tmp0, float tmp1, float tmp2, float& e0,
+                                               float& e1, float& e2) {
+  e0 = (sc * tmp0 + 0.0f * tmp1) + t_x;
+  e1 = (0.0f * tmp0 + sc * tmp1) + t_y;
+  e2 = tmp2;
+}
+
+// level epilogue: the level's estimate back in the world, heading normalised
+__device__ __forceinline__ void gn_level_end(float sc, float t_x, float t_y, float e0, float e1, float e2, float& tmp0,
+                                             float& tmp1, float& tmp2) {
+  // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
+  const double two_pi = 2.0f * 3.14159265358979323846;
+  float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
+  if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
+  // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
+  const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
+  const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
+  const float wt0 = -(l00 * t_x + l01 * t_y), wt1 = -(l10 * t_x + l11 * t_y);
+  tmp0 = (l00 * e0 + l01 * e1) + wt0;
+  tmp1 = (l10 * e0 + l11 * e1) + wt1;
+  tmp2 = a;
+}
+
+// bilinear map value and gradient {v, gxv, gyv} from the four cell probabilities (interpMapValueWithDerivatives,
+// OccGridMapUtil.h:77-139); `in_map` false: all three are 0 (the straight-line forms read cell 0 for such a point and mask it
+// here).  The mask and the array result are deliberate: with three float& results and the callers masking afterwards hipcc split
+// gn_chunk's loads into two dependent groups (k_gn_match_reg<512,3>: its six 8-byte loads as 2 + 4 with a wait in between) and
+// a match took 36.63 / 36.90 / 36.65 us against 34.59 / 34.61 / 34.49 with the statements written out (MI355X, three
+// alternating runs; DESIGN.md 4.14 "One matcher body" has the table of the form below, which keeps every kernel's load groups).
+__device__ __forceinline__ void gn_interp(float i0, float i1, float i2, float i3, float fx, float fy, bool in_map, float* out) {
+  const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
+  const float xi = 1.0f - fx, yi = 1.0f - fy;
+  const float v = in_map ? ((i0 * xi + i1 * fx) * (yi)) + ((i2 * xi + i3 * fx) * (fy)) : 0.0f;
+  const float gxv = in_map ? -((dx1 * yi) + (dx2 * fy)) : 0.0f;
+  const float gyv = in_map ? -((dy1 * xi) + (dy2 * fx)) : 0.0f;
+  out[0] = v; out[1] = gxv; out[2] = gyv;
+}
+
+// one point's nine products (getCompleteHessianDerivs, OccGridMapUtil.h:141-183): dTr[0..2], then H's 00 11 22 01 02 12
+template <bool ADD>
+__device__ __forceinline__ void gn_terms9(float gxv, float gyv, float funVal, float rotDeriv, float* t) {
+  const float p[9] = {gxv * funVal, gyv * funVal, rotDeriv * funVal, gxv * gxv, gyv * gyv, rotDeriv * rotDeriv,
+                      gxv * gyv, gxv * rotDeriv, gyv * rotDeriv};
+#pragma unroll
+  for (int q = 0; q < 9; q++) t[q] = ADD ? t[q] + p[q] : p[q];
+}
+
 // (the body of k_gn_match; k_gn_match_batch_ordered runs the same statements with one block per entry of a batch)
 __device__ __forceinline__ void gn_match_ordered(const GnLevels& lv, const float* __restrict__ pts, int n, float bx, float by,
                                                  float bth, float* __restrict__ out_pose /* [3] */,
@@ -720,11 +791,7 @@ __device__ __forceinline__ void gn_match_ordered(const GnLevels& lv, const float
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : (float)(1.0 / pow(2.0, (double)L));
     const int iters = 1 + (L == 0 ? 5 : 3);
-    if (tid == 0) {  // getMapCoordsPose (GridMapBase.h:238-242)
-      s_est[0] = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];
-      s_est[1] = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-      s_est[2] = tmp2;
-    }
+    if (tid == 0) gn_level_begin(sc, lv.t_x[L], lv.t_y[L], tmp0, tmp1, tmp2, s_est[0], s_est[1], s_est[2]);
     __syncthreads();
     for (int it = 0; it < iters; it++) {
       const float e0 = s_est[0], e1 = s_est[1], e2 = s_est[2];
@@ -737,22 +804,15 @@ __device__ __forceinline__ void gn_match_ordered(const GnLevels& lv, const float
         float v = 0.0f, gxv = 0.0f, gyv = 0.0f;
         if (!(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y)) {  // pointOutOfMapBounds (:60-63)
           const int ix = (int)cx, iy = (int)cy;
-          const float fx = cx - (float)ix, fy = cy - (float)iy;
           const int index = iy * sx + ix;
-          const float i0 = gn_prob(lo, index), i1 = gn_prob(lo, index + 1);
-          const float i2 = gn_prob(lo, index + sx), i3 = gn_prob(lo, index + sx + 1);
-          const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-          const float xi = 1.0f - fx, yi = 1.0f - fy;
-          v = ((i0 * xi + i1 * fx) * (yi)) + ((i2 * xi + i3 * fx) * (fy));
-          gxv = -((dx1 * yi) + (dx2 * fy));
-          gyv = -((dy1 * xi) + (dy2 * fx));
+          float o[3];
+          gn_interp(gn_prob(lo, index), gn_prob(lo, index + 1), gn_prob(lo, index + sx), gn_prob(lo, index + sx + 1),
+                    cx - (float)ix, cy - (float)iy, true, o);
+          v = o[0]; gxv = o[1]; gyv = o[2];
         }
         const float funVal = 1.0f - v;
         const float rotDeriv = ((-s * px - c * py) * gxv + (c * px - s * py) * gyv);
-        float* t = terms + 9 * i;
-        t[0] = gxv * funVal; t[1] = gyv * funVal; t[2] = rotDeriv * funVal;
-        t[3] = gxv * gxv; t[4] = gyv * gyv; t[5] = rotDeriv * rotDeriv;
-        t[6] = gxv * gyv; t[7] = gxv * rotDeriv; t[8] = gyv * rotDeriv;
+        gn_terms9<false>(gxv, gyv, funVal, rotDeriv, terms + 9 * i);
       }
       __syncthreads();
       // sequential fp32 accumulation in point order (:94-126): the nine sums are independent chains, so
@@ -764,40 +824,10 @@ __device__ __forceinline__ void gn_match_ordered(const GnLevels& lv, const float
         s_sum[tid] = acc;
       }
       __syncthreads();
-      if (tid == 0) {
-        const float d0 = s_sum[0], d1 = s_sum[1], d2 = s_sum[2], h00 = s_sum[3], h11 = s_sum[4], h22 = s_sum[5],
-                    h01 = s_sum[6], h02 = s_sum[7], h12 = s_sum[8];
-        float H[9] = {h00, h01, h02, h01, h11, h12, h02, h12, h22};
-        for (int q = 0; q < 9; q++) Hlast[q] = H[q];
-        if (h00 != 0.0f && h11 != 0.0f) {  // estimateTransformationLogLh (ScanMatcher.h:113-133)
-          const float c0 = gn_cof3(H, 0, 0), c1 = gn_cof3(H, 1, 0), c2 = gn_cof3(H, 2, 0);
-          const float det = c0 * H[0] + (c1 * H[3] + c2 * H[6]);
-          const float invdet = 1.0f / det;
-          const float Hi[9] = {c0 * invdet, c1 * invdet, c2 * invdet,
-                               gn_cof3(H, 0, 1) * invdet, gn_cof3(H, 1, 1) * invdet, gn_cof3(H, 2, 1) * invdet,
-                               gn_cof3(H, 0, 2) * invdet, gn_cof3(H, 1, 2) * invdet, gn_cof3(H, 2, 2) * invdet};
-          float sd[3];
-          // H.inverse() * dTr: Eigen's coefficient-based product sums a 3-term row as a0 + (a1 + a2) (Core/Redux.h)
-          for (int r = 0; r < 3; r++) sd[r] = Hi[3 * r] * d0 + (Hi[3 * r + 1] * d1 + Hi[3 * r + 2] * d2);
-          if (sd[2] > 0.2f) sd[2] = 0.2f; else if (sd[2] < -0.2f) sd[2] = -0.2f;
-          s_est[0] += sd[0]; s_est[1] += sd[1]; s_est[2] += sd[2];
-        }
-      }
+      if (tid == 0) gn_solve_step(s_sum, Hlast, s_est[0], s_est[1], s_est[2]);
       __syncthreads();
     }
-    if (tid == 0) {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)s_est[2], two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * s_est[0] + l01 * s_est[1]) + wt0;
-      tmp1 = (l10 * s_est[0] + l11 * s_est[1]) + wt1;
-      tmp2 = a;
-    }
+    if (tid == 0) gn_level_end(sc, lv.t_x[L], lv.t_y[L], s_est[0], s_est[1], s_est[2], tmp0, tmp1, tmp2);
     __syncthreads();
   }
   if (tid == 0) {
@@ -826,6 +856,8 @@ k_gn_match(GnLevels lv, const float* __restrict__ pts, int n, float bx, float by
 // code).  Points are staged once in LDS; the kernel also writes the cached container (MapRepMultiMap.h:161) when the
 // points come from pinned host memory, and its result lands in pinned host memory: no copy operation on the stream.
 // LSLAM_MAP_OPT_ORDERED_SUMS selects the ordered kernel (the bit comparison with the restatement).
+// The matcher itself is gn_match_fast_body / gn_match_reg_body, which hand pose[3] and H[9] back in every thread: the
+// single-call kernels here write them out with the ticket, the streamed k_hs_match_* go on to the update decision.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float gn_row16_sum(float v) {  // every lane of a 16-lane row ends up with the row's sum
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
@@ -887,14 +919,38 @@ __device__ __forceinline__ void gn_sincos(float x, float* sn, float* cs) {
   *cs = ((q + 1) & 2) ? -c0 : c0;
 }
 
-__device__ __forceinline__ void gn_solve_step_fwd(const float* sum, float* H, float& e0, float& e1, float& e2);
-template <int NT>
-__global__ void __launch_bounds__(NT)
-k_gn_match_fast(GnLevels lv, const float* __restrict__ pts, float* __restrict__ cache_dst, int n, int pts_in_lds, float bx,
-                float by, float bth, float* __restrict__ out /* pose[3] + H[9], [15] = ticket */, int ticket) {
-  extern __shared__ float s_pts[];  // [2n] when pts_in_lds
-  constexpr int NW = NT / 64;
+// The waves' nine totals meet in LDS: lane q < 9 of every wave adds the NW partials of sum q (NW LDS reads instead of 9 NW per
+// lane) and readlane hands the nine block sums to all lanes.  Two buffers: the next iteration writes the other one, so an
+// iteration has ONE barrier.  wave_total(q) is this wave's total of sum q, valid in the lanes where `writer` holds; it is
+// evaluated right in front of its store, so a total that comes out of readlanes (gn_wave_sum) does not wait in scalar
+// registers for the other eight.  That is why it is a callable and not nine values: with all nine totals computed first the
+// compiler reports 106 SGPRs instead of 86 for k_hs_match_fast<NT> (97 instead of 74 for k_gn_match_fast<NT>), and
+// k_hs_match_fast<256> drops from 8 waves per SIMD to 7.
+template <int NW, class WaveTotal>
+__device__ __forceinline__ void gn_block_sums9(WaveTotal wave_total, bool writer, int wv, int lane, int& flip, float* sum) {
   __shared__ float s_part[2][NW][12];
+#pragma unroll
+  for (int q = 0; q < 9; q++) {
+    const float t = wave_total(q);
+    if (writer) s_part[flip][wv][q] = t;
+  }
+  __syncthreads();
+  float mine = 0.0f;
+  if (lane < 9) {
+    mine = s_part[flip][0][lane];
+#pragma unroll
+    for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
+  }
+#pragma unroll
+  for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
+  flip ^= 1;
+}
+
+// the staged-points form: a container of any length, its points in LDS (pts_in_lds) or read back from memory
+template <int NT>
+__device__ __forceinline__ void gn_match_fast_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
+                                                   int n, int pts_in_lds, float bx, float by, float bth, float* pose, float* H) {
+  extern __shared__ float s_pts[];  // [2n] when pts_in_lds
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   for (int i = tid; i < 2 * n; i += NT) {
     const float v = pts[i];
@@ -904,7 +960,8 @@ k_gn_match_fast(GnLevels lv, const float* __restrict__ pts, float* __restrict__ 
   const float* P = pts_in_lds ? s_pts : (cache_dst ? cache_dst : pts);
   __syncthreads();  // (a thread reads points other threads staged; cache_dst is only re-read by its own writers' block)
   float tmp0 = bx, tmp1 = by, tmp2 = bth;
-  float H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int q = 0; q < 9; q++) H[q] = 0.0f;
   int flip = 0;
   for (int L = lv.n_levels - 1; L >= 0; --L) {
     if (n == 0) continue;
@@ -913,10 +970,8 @@ k_gn_match_fast(GnLevels lv, const float* __restrict__ pts, float* __restrict__ 
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
     const int iters = 1 + (L == 0 ? 5 : 3);
-    // getMapCoordsPose (GridMapBase.h:238-242)
-    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];
-    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-    float e2 = tmp2;
+    float e0, e1, e2;
+    gn_level_begin(sc, lv.t_x[L], lv.t_y[L], tmp0, tmp1, tmp2, e0, e1, e2);
     const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
     for (int it = 0; it < iters; it++) {
       float s, c;
@@ -930,100 +985,90 @@ k_gn_match_fast(GnLevels lv, const float* __restrict__ pts, float* __restrict__ 
         float v = 0.0f, gxv = 0.0f, gyv = 0.0f;
         if (!(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y)) {  // pointOutOfMapBounds (:60-63)
           const int ix = (int)cx, iy = (int)cy;
-          const float fx = cx - (float)ix, fy = cy - (float)iy;
           const int index = iy * sx + ix;
           const float l0 = lo[index], l1 = lo[index + 1], l2 = lo[index + sx], l3 = lo[index + sx + 1];
-          const float i0 = gn_prob_f(l0), i1 = gn_prob_f(l1), i2 = gn_prob_f(l2), i3 = gn_prob_f(l3);
-          const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-          const float xi = 1.0f - fx, yi = 1.0f - fy;
-          v = ((i0 * xi + i1 * fx) * (yi)) + ((i2 * xi + i3 * fx) * (fy));
-          gxv = -((dx1 * yi) + (dx2 * fy));
-          gyv = -((dy1 * xi) + (dy2 * fx));
+          float o[3];
+          gn_interp(gn_prob_f(l0), gn_prob_f(l1), gn_prob_f(l2), gn_prob_f(l3), cx - (float)ix, cy - (float)iy, true, o);
+          v = o[0]; gxv = o[1]; gyv = o[2];
         }
         const float funVal = 1.0f - v;
         const float rotDeriv = ((-s * px - c * py) * gxv + (c * px - s * py) * gyv);
-        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
-        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
-        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
-      }
-#pragma unroll
-      for (int q = 0; q < 9; q++) {
-        const float t = gn_wave_sum(acc[q]);
-        if (lane == 0) s_part[flip][wv][q] = t;
-      }
-      __syncthreads();
-      // lane q < 9 of every wave adds the NW partials of sum q (NW LDS reads instead of 9 NW per lane), readlane hands
-      // the nine totals to all lanes
-      float mine = 0.0f;
-      if (lane < 9) {
-        mine = s_part[flip][0][lane];
-#pragma unroll
-        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
+        gn_terms9<true>(gxv, gyv, funVal, rotDeriv, acc);
       }
       float sum[9];
-#pragma unroll
-      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
-      flip ^= 1;  // the next iteration writes the other buffer: no second barrier needed
-      gn_solve_step_fwd(sum, H, e0, e1, e2);
+      gn_block_sums9<NT / 64>([&](int q) { return gn_wave_sum(acc[q]); }, lane == 0, wv, lane, flip, sum);
+      gn_solve_step(sum, H, e0, e1, e2);
     }
-    {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * e0 + l01 * e1) + wt0;
-      tmp1 = (l10 * e0 + l11 * e1) + wt1;
-      tmp2 = a;
-    }
+    gn_level_end(sc, lv.t_x[L], lv.t_y[L], e0, e1, e2, tmp0, tmp1, tmp2);
   }
-  if (tid == 0) {
-    out[0] = tmp0; out[1] = tmp1; out[2] = tmp2;
-    for (int q = 0; q < 9; q++) out[3 + q] = H[q];
-    // `out` is pinned host memory: a system-scope fence, then the caller's ticket -- the host spins on it instead of waiting
-    // for the stream (the completion signal + wake-up cost several microseconds of a 34 us match)
-    __threadfence_system();
-    ((volatile int*)out)[15] = ticket;
-  }
+  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
 }
 
-// The solve + pose update every thread performs after the sums (estimateTransformationLogLh, ScanMatcher.h:113-133)
-__device__ __forceinline__ void gn_solve_step(const float* sum, float* H, float& e0, float& e1, float& e2);
-__device__ __forceinline__ void gn_solve_step_fwd(const float* sum, float* H, float& e0, float& e1, float& e2) { gn_solve_step(sum, H, e0, e1, e2); }
-__device__ __forceinline__ void gn_solve_step(const float* sum, float* H, float& e0, float& e1, float& e2) {
-  const float d0 = sum[0], d1 = sum[1], d2 = sum[2], h00 = sum[3], h11 = sum[4], h22 = sum[5], h01 = sum[6], h02 = sum[7],
-              h12 = sum[8];
-  H[0] = h00; H[1] = h01; H[2] = h02; H[3] = h01; H[4] = h11; H[5] = h12; H[6] = h02; H[7] = h12; H[8] = h22;
-  if (h00 != 0.0f && h11 != 0.0f) {
-    const float c0 = gn_cof3(H, 0, 0), c1 = gn_cof3(H, 1, 0), c2 = gn_cof3(H, 2, 0);
-    const float det = c0 * H[0] + (c1 * H[3] + c2 * H[6]);
-    const float invdet = 1.0f / det;
-    const float Hi[9] = {c0 * invdet, c1 * invdet, c2 * invdet,
-                         gn_cof3(H, 0, 1) * invdet, gn_cof3(H, 1, 1) * invdet, gn_cof3(H, 2, 1) * invdet,
-                         gn_cof3(H, 0, 2) * invdet, gn_cof3(H, 1, 2) * invdet, gn_cof3(H, 2, 2) * invdet};
-    float sd[3];
-    for (int r = 0; r < 3; r++) sd[r] = Hi[3 * r] * d0 + (Hi[3 * r + 1] * d1 + Hi[3 * r + 2] * d2);
-    if (sd[2] > 0.2f) sd[2] = 0.2f; else if (sd[2] < -0.2f) sd[2] = -0.2f;
-    e0 += sd[0]; e1 += sd[1]; e2 += sd[2];
-  }
+// A single call's result, one thread: `out` is pinned host memory -- a system-scope fence, then the caller's ticket; the host
+// spins on it instead of waiting for the stream (the completion signal + wake-up cost several microseconds of a 34 us match)
+__device__ __forceinline__ void gn_write_result(float* __restrict__ out, const float* pose, const float* H, int ticket) {
+  out[0] = pose[0]; out[1] = pose[1]; out[2] = pose[2];
+  for (int q = 0; q < 9; q++) out[3 + q] = H[q];
+  __threadfence_system();
+  ((volatile int*)out)[15] = ticket;
 }
 
-// k_gn_match_reg<NT, PMAX> -- k_gn_match_fast for scans of at most NT * PMAX points (every real LaserScan: 1081 beams =
-// 512 x 3), the form that runs.  The generic kernel above walks its points one after the other, and each costs a
-// dependent LDS read, then a dependent round trip to L2 for the four map cells: ~3.4 us per Gauss-Newton iteration of
-// mostly waiting.  Here a thread's <= PMAX points live in REGISTERS for the whole match (no LDS, no barrier in front of
-// the first iteration), and an iteration is straight-line code: all cell addresses first -- an out-of-map point reads
-// cell 0 and is masked afterwards, so no load sits behind a branch --, then the 4 * PMAX loads back to back, then the
-// arithmetic.  One L2 round trip per iteration instead of PMAX.
-template <int NT, int PMAX>
+template <int NT>
 __global__ void __launch_bounds__(NT)
-k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ cache_dst, int n, float bx, float by, float bth,
-               float* __restrict__ out /* pose[3] + H[9], [15] = ticket */, int ticket) {
-  constexpr int NW = NT / 64;
-  __shared__ float s_part[2][NW][12];
+k_gn_match_fast(GnLevels lv, const float* __restrict__ pts, float* __restrict__ cache_dst, int n, int pts_in_lds, float bx,
+                float by, float bth, float* __restrict__ out /* pose[3] + H[9], [15] = ticket */, int ticket) {
+  float pose[3], H[9];
+  gn_match_fast_body<NT>(lv, pts, cache_dst, n, pts_in_lds, bx, by, bth, pose, H);
+  if (threadIdx.x == 0) gn_write_result(out, pose, H, ticket);
+}
+
+// One straight-line pass over CH points per lane, the pattern of the register-points form and of the batch kernel: all cell
+// addresses first -- an out-of-map point reads cell 0 and is masked afterwards, so no load sits behind a branch --, then the
+// 4 * CH loads back to back, then the arithmetic.  One L2 round trip per pass instead of CH.  have[p] false: no point (its
+// funVal is 0 as well, so it adds nothing to any sum).
+template <int CH>
+__device__ __forceinline__ void gn_chunk(const float* __restrict__ lo, int sx, float lim_x, float lim_y, float s, float c, float e0,
+                                         float e1, const float* px, const float* py, const bool* have, float* acc) {
+  int idx[CH];
+  float fx[CH], fy[CH];
+  bool inb[CH];
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    const float cx = (c * px[p] + (-s) * py[p]) + e0;
+    const float cy = (s * px[p] + c * py[p]) + e1;
+    inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
+    const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;
+    fx[p] = cx - (float)ix;
+    fy[p] = cy - (float)iy;
+    idx[p] = iy * sx + ix;
+  }
+  float l0[CH], l1[CH], l2[CH], l3[CH];
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    l0[p] = lo[idx[p]];
+    l1[p] = lo[idx[p] + 1];
+    l2[p] = lo[idx[p] + sx];
+    l3[p] = lo[idx[p] + sx + 1];
+  }
+#pragma unroll
+  for (int p = 0; p < CH; p++) {
+    float o[3];
+    gn_interp(gn_prob_f(l0[p]), gn_prob_f(l1[p]), gn_prob_f(l2[p]), gn_prob_f(l3[p]), fx[p], fy[p], inb[p], o);
+    const float v = o[0], gxv = o[1], gyv = o[2];
+    const float funVal = have[p] ? 1.0f - v : 0.0f;
+    const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
+    gn_terms9<true>(gxv, gyv, funVal, rotDeriv, acc);
+  }
+}
+
+// The register-points form: gn_match_fast_body for scans of at most NT * PMAX points (every real LaserScan: 1081 beams =
+// 512 x 3), the form that runs.  The staged form walks its points one after the other, and each costs a dependent LDS read,
+// then a dependent round trip to L2 for the four map cells: ~3.4 us per Gauss-Newton iteration of mostly waiting.  Here a
+// thread's <= PMAX points live in REGISTERS for the whole match (no LDS, no barrier in front of the first iteration), and an
+// iteration is one gn_chunk<PMAX>.
+template <int NT, int PMAX>
+__device__ __forceinline__ void gn_match_reg_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
+                                                  int n, float bx, float by, float bth, float* pose, float* H) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   float px0[PMAX], py0[PMAX];
   bool have[PMAX];
@@ -1040,7 +1085,8 @@ k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ c
     py0[p] = v.y;
   }
   float tmp0 = bx, tmp1 = by, tmp2 = bth;
-  float H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int q = 0; q < 9; q++) H[q] = 0.0f;
   int flip = 0;
   for (int L = lv.n_levels - 1; L >= 0; --L) {
     if (n == 0) continue;
@@ -1049,9 +1095,8 @@ k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ c
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
     const int iters = 1 + (L == 0 ? 5 : 3);
-    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
-    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-    float e2 = tmp2;
+    float e0, e1, e2;
+    gn_level_begin(sc, lv.t_x[L], lv.t_y[L], tmp0, tmp1, tmp2, e0, e1, e2);
     const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
     float px[PMAX], py[PMAX];
 #pragma unroll
@@ -1062,82 +1107,25 @@ k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ c
     for (int it = 0; it < iters; it++) {
       float s, c;
       gn_sincos(e2, &s, &c);
-      int idx[PMAX];
-      float fx[PMAX], fy[PMAX];
-      bool inb[PMAX];
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        const float cx = (c * px[p] + (-s) * py[p]) + e0;
-        const float cy = (s * px[p] + c * py[p]) + e1;
-        inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
-        const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;
-        fx[p] = cx - (float)ix;
-        fy[p] = cy - (float)iy;
-        idx[p] = iy * sx + ix;
-      }
-      float l0[PMAX], l1[PMAX], l2[PMAX], l3[PMAX];
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        l0[p] = lo[idx[p]];
-        l1[p] = lo[idx[p] + 1];
-        l2[p] = lo[idx[p] + sx];
-        l3[p] = lo[idx[p] + sx + 1];
-      }
       float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        const float i0 = gn_prob_f(l0[p]), i1 = gn_prob_f(l1[p]), i2 = gn_prob_f(l2[p]), i3 = gn_prob_f(l3[p]);
-        const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-        const float xi = 1.0f - fx[p], yi = 1.0f - fy[p];
-        const float v = inb[p] ? ((i0 * xi + i1 * fx[p]) * (yi)) + ((i2 * xi + i3 * fx[p]) * (fy[p])) : 0.0f;
-        const float gxv = inb[p] ? -((dx1 * yi) + (dx2 * fy[p])) : 0.0f;
-        const float gyv = inb[p] ? -((dy1 * xi) + (dy2 * fx[p])) : 0.0f;
-        const float funVal = have[p] ? 1.0f - v : 0.0f;
-        const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
-        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
-        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
-        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
-      }
-      gn_wave_sums9(acc);
-      if (lane == 63) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) s_part[flip][wv][q] = acc[q];
-      }
-      __syncthreads();
-      float mine = 0.0f;
-      if (lane < 9) {
-        mine = s_part[flip][0][lane];
-#pragma unroll
-        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
-      }
+      gn_chunk<PMAX>(lo, sx, lim_x, lim_y, s, c, e0, e1, px, py, have, acc);
+      gn_wave_sums9(acc);  // totals in lane 63
       float sum[9];
-#pragma unroll
-      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
-      flip ^= 1;  // the next iteration writes the other buffer: one barrier per iteration
+      gn_block_sums9<NT / 64>([&](int q) { return acc[q]; }, lane == 63, wv, lane, flip, sum);
       gn_solve_step(sum, H, e0, e1, e2);
     }
-    {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * e0 + l01 * e1) + wt0;
-      tmp1 = (l10 * e0 + l11 * e1) + wt1;
-      tmp2 = a;
-    }
+    gn_level_end(sc, lv.t_x[L], lv.t_y[L], e0, e1, e2, tmp0, tmp1, tmp2);
   }
-  if (tid == 0) {
-    out[0] = tmp0; out[1] = tmp1; out[2] = tmp2;
-    for (int q = 0; q < 9; q++) out[3 + q] = H[q];
-    // `out` is pinned host memory: a system-scope fence, then the caller's ticket -- the host spins on it instead of waiting
-    // for the stream (the completion signal + wake-up cost several microseconds of a 34 us match)
-    __threadfence_system();
-    ((volatile int*)out)[15] = ticket;
-  }
+  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ cache_dst, int n, float bx, float by, float bth,
+               float* __restrict__ out /* pose[3] + H[9], [15] = ticket */, int ticket) {
+  float pose[3], H[9];
+  gn_match_reg_body<NT, PMAX>(lv, pts, cache_dst, n, bx, by, bth, pose, H);
+  if (threadIdx.x == 0) gn_write_result(out, pose, H, ticket);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1149,54 +1137,12 @@ k_gn_match_reg(GnLevels lv, const float* __restrict__ pts, float* __restrict__ c
 // A wave walks its container from memory every iteration, kGnBatchChunk points per lane at a time (point i belongs to lane
 // i % 64; the reads are coalesced float2 and stay in L1 / L2 -- 8.6 KB for a 1081-beam scan), whatever the container's size:
 // ONE form, no switch point.  Holding a 1081-point scan in registers instead (17 points per lane, fully unrolled) was
-// tried and dropped: under the 128-VGPR cap hipcc spilled ~700 bytes per lane to scratch at every chunk size.  Each chunk is
-// k_gn_match_reg's straight-line pattern: all cell addresses, then the 4 * CH loads back to back, then the shipped per-point
-// arithmetic.  <= 128 VGPRs: four waves per SIMD stay resident and cover one another's L2 round trips, which is what bounds
+// tried and dropped: under the 128-VGPR cap hipcc spilled ~700 bytes per lane to scratch at every chunk size.  Each pass is
+// one gn_chunk.  <= 128 VGPRs: four waves per SIMD stay resident and cover one another's L2 round trips, which is what bounds
 // the single-match kernel.
 // ------------------------------------------------------------------------------------------
 constexpr int kGnBatchWaves = 4;                        // entries per block
 constexpr int kGnBatchChunk = 6;  // points per lane whose four cell loads each are in flight together (384 per wave and pass)
-
-template <int CH>
-__device__ __forceinline__ void gn_batch_chunk(const float* __restrict__ lo, int sx, float lim_x, float lim_y, float s, float c,
-                                               float e0, float e1, const float* px, const float* py, const bool* have,
-                                               float* acc) {
-  int idx[CH];
-  float fx[CH], fy[CH];
-  bool inb[CH];
-#pragma unroll
-  for (int p = 0; p < CH; p++) {
-    const float cx = (c * px[p] + (-s) * py[p]) + e0;
-    const float cy = (s * px[p] + c * py[p]) + e1;
-    inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
-    const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;             // (an out-of-map point reads cell 0, masked below)
-    fx[p] = cx - (float)ix;
-    fy[p] = cy - (float)iy;
-    idx[p] = iy * sx + ix;
-  }
-  float l0[CH], l1[CH], l2[CH], l3[CH];
-#pragma unroll
-  for (int p = 0; p < CH; p++) {
-    l0[p] = lo[idx[p]];
-    l1[p] = lo[idx[p] + 1];
-    l2[p] = lo[idx[p] + sx];
-    l3[p] = lo[idx[p] + sx + 1];
-  }
-#pragma unroll
-  for (int p = 0; p < CH; p++) {
-    const float i0 = gn_prob_f(l0[p]), i1 = gn_prob_f(l1[p]), i2 = gn_prob_f(l2[p]), i3 = gn_prob_f(l3[p]);
-    const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-    const float xi = 1.0f - fx[p], yi = 1.0f - fy[p];
-    const float v = inb[p] ? ((i0 * xi + i1 * fx[p]) * (yi)) + ((i2 * xi + i3 * fx[p]) * (fy[p])) : 0.0f;
-    const float gxv = inb[p] ? -((dx1 * yi) + (dx2 * fy[p])) : 0.0f;
-    const float gyv = inb[p] ? -((dy1 * xi) + (dy2 * fx[p])) : 0.0f;
-    const float funVal = have[p] ? 1.0f - v : 0.0f;
-    const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
-    acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
-    acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
-    acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
-  }
-}
 
 __global__ void __launch_bounds__(64 * kGnBatchWaves) __attribute__((amdgpu_waves_per_eu(4)))
 k_gn_match_batch(GnLevels lv, const float* __restrict__ pts, const int2* __restrict__ ent /* [n_entries]: first point, points */,
@@ -1218,9 +1164,8 @@ k_gn_match_batch(GnLevels lv, const float* __restrict__ pts, const int2* __restr
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
     const int iters = 1 + (L == 0 ? 5 : 3);
-    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
-    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-    float e2 = tmp2;
+    float e0, e1, e2;
+    gn_level_begin(sc, lv.t_x[L], lv.t_y[L], tmp0, tmp1, tmp2, e0, e1, e2);
     const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
     for (int it = 0; it < iters; it++) {
       float s, c;
@@ -1238,7 +1183,7 @@ k_gn_match_batch(GnLevels lv, const float* __restrict__ pts, const int2* __restr
           px[j] = v.x * factor;
           py[j] = v.y * factor;
         }
-        gn_batch_chunk<CH>(lo, sx, lim_x, lim_y, s, c, e0, e1, px, py, have, acc);
+        gn_chunk<CH>(lo, sx, lim_x, lim_y, s, c, e0, e1, px, py, have, acc);
       }
       gn_wave_sums9(acc);  // totals in lane 63
       float sum[9];
@@ -1246,19 +1191,7 @@ k_gn_match_batch(GnLevels lv, const float* __restrict__ pts, const int2* __restr
       for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc[q]), 63));
       gn_solve_step(sum, H, e0, e1, e2);
     }
-    {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * e0 + l01 * e1) + wt0;
-      tmp1 = (l10 * e0 + l11 * e1) + wt1;
-      tmp2 = a;
-    }
+    gn_level_end(sc, lv.t_x[L], lv.t_y[L], e0, e1, e2, tmp0, tmp1, tmp2);
   }
   if (lane == 0) {
     out_pose[3 * e] = tmp0; out_pose[3 * e + 1] = tmp1; out_pose[3 * e + 2] = tmp2;
@@ -1287,8 +1220,9 @@ k_gn_match_batch_ordered(GnLevels lv, const float* __restrict__ pts, const int2*
 // per call.  No hand-over words, no spinning kernel, no cooperative launch: stream order is the only ordering.
 //   HsState        the processor's three state vectors and covariance, the live and the cached container's counts, the
 //                  cached origo, this scan's decision and -- per level -- what update_impl fills into LevelGeom on the host
-//   k_hs_match_*   k_gn_match_reg's / k_gn_match_fast's statements (hs_match_*_body, a copy) on a count and a start pose read from the device (same bits as
-//                  lslam_map_match_data for the same container, start pose, map and LSLAM_GN_THREADS); its last phase, one
+//   k_hs_match_*   gn_match_reg_body / gn_match_fast_body -- the one matcher lslam_map_match_data runs -- on a count and a
+//                  start pose read from the device (same bits as lslam_map_match_data for the same container, start pose,
+//                  map and LSLAM_GN_THREADS: tests/test_hector_stream_gpu.py holds it to that); its last phase, one
 //                  thread, is the gate (H/util/UtilFunctions.h:72-91) and the geometry of every level
 //   k_hs_mark / k_hs_apply   logodds_mark_wave / logodds_apply_wave (the two-kernel, non-deferred update) with geometry,
 //                  point pointer and count read from HsState; all levels in one launch each (blockIdx.y = level), the grid
@@ -1345,219 +1279,6 @@ __device__ __forceinline__ bool hs_pose_difference_larger_than(const float* p, c
   else if ((double)ad < -pi) ad = (float)((double)ad + pi * 2.0);
   if (fabs_gate) return fabsf(ad) > min_angle;
   return (float)abs((int)ad) > min_angle;
-}
-
-// The matcher of the streamed kernels: the statements of k_gn_match_fast / k_gn_match_reg, DUPLICATED as device functions
-// that hand pose[3] and H[9] back in every thread (the existing kernels stay exactly as they were compiled; sharing one body
-// re-scheduled them).  Keep the two pairs in step: a change to the arithmetic of one belongs in the other.
-template <int NT>
-__device__ __forceinline__ void hs_match_fast_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
-                                                   int n, int pts_in_lds, float bx, float by, float bth, float* pose, float* H) {
-  extern __shared__ float s_pts[];  // [2n] when pts_in_lds
-  constexpr int NW = NT / 64;
-  __shared__ float s_part[2][NW][12];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (int i = tid; i < 2 * n; i += NT) {
-    const float v = pts[i];
-    if (pts_in_lds) s_pts[i] = v;
-    if (cache_dst) cache_dst[i] = v;
-  }
-  const float* P = pts_in_lds ? s_pts : (cache_dst ? cache_dst : pts);
-  __syncthreads();  // (a thread reads points other threads staged; cache_dst is only re-read by its own writers' block)
-  float tmp0 = bx, tmp1 = by, tmp2 = bth;
-#pragma unroll
-  for (int q = 0; q < 9; q++) H[q] = 0.0f;
-  int flip = 0;
-  for (int L = lv.n_levels - 1; L >= 0; --L) {
-    if (n == 0) continue;
-    const float* lo = lv.logodds[L];
-    const int sx = lv.sx[L], sy = lv.sy[L];
-    const float sc = lv.scale[L];
-    const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
-    const int iters = 1 + (L == 0 ? 5 : 3);
-    // getMapCoordsPose (GridMapBase.h:238-242)
-    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];
-    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-    float e2 = tmp2;
-    const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
-    for (int it = 0; it < iters; it++) {
-      float s, c;
-      sincosf(e2, &s, &c);
-      float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll 2
-      for (int i = tid; i < n; i += NT) {
-        const float px = P[2 * i] * factor, py = P[2 * i + 1] * factor;
-        const float cx = (c * px + (-s) * py) + e0;
-        const float cy = (s * px + c * py) + e1;
-        float v = 0.0f, gxv = 0.0f, gyv = 0.0f;
-        if (!(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y)) {  // pointOutOfMapBounds (:60-63)
-          const int ix = (int)cx, iy = (int)cy;
-          const float fx = cx - (float)ix, fy = cy - (float)iy;
-          const int index = iy * sx + ix;
-          const float l0 = lo[index], l1 = lo[index + 1], l2 = lo[index + sx], l3 = lo[index + sx + 1];
-          const float i0 = gn_prob_f(l0), i1 = gn_prob_f(l1), i2 = gn_prob_f(l2), i3 = gn_prob_f(l3);
-          const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-          const float xi = 1.0f - fx, yi = 1.0f - fy;
-          v = ((i0 * xi + i1 * fx) * (yi)) + ((i2 * xi + i3 * fx) * (fy));
-          gxv = -((dx1 * yi) + (dx2 * fy));
-          gyv = -((dy1 * xi) + (dy2 * fx));
-        }
-        const float funVal = 1.0f - v;
-        const float rotDeriv = ((-s * px - c * py) * gxv + (c * px - s * py) * gyv);
-        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
-        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
-        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
-      }
-#pragma unroll
-      for (int q = 0; q < 9; q++) {
-        const float t = gn_wave_sum(acc[q]);
-        if (lane == 0) s_part[flip][wv][q] = t;
-      }
-      __syncthreads();
-      // lane q < 9 of every wave adds the NW partials of sum q (NW LDS reads instead of 9 NW per lane), readlane hands
-      // the nine totals to all lanes
-      float mine = 0.0f;
-      if (lane < 9) {
-        mine = s_part[flip][0][lane];
-#pragma unroll
-        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
-      }
-      float sum[9];
-#pragma unroll
-      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
-      flip ^= 1;  // the next iteration writes the other buffer: no second barrier needed
-      gn_solve_step(sum, H, e0, e1, e2);
-    }
-    {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * e0 + l01 * e1) + wt0;
-      tmp1 = (l10 * e0 + l11 * e1) + wt1;
-      tmp2 = a;
-    }
-  }
-  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
-}
-
-template <int NT, int PMAX>
-__device__ __forceinline__ void hs_match_reg_body(const GnLevels& lv, const float* __restrict__ pts, float* __restrict__ cache_dst,
-                                                  int n, float bx, float by, float bth, float* pose, float* H) {
-  constexpr int NW = NT / 64;
-  __shared__ float s_part[2][NW][12];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float px0[PMAX], py0[PMAX];
-  bool have[PMAX];
-#pragma unroll
-  for (int p = 0; p < PMAX; p++) {
-    const int i = tid + p * NT;
-    have[p] = i < n;
-    float2 v = make_float2(0.0f, 0.0f);
-    if (have[p]) {
-      v = reinterpret_cast<const float2*>(pts)[i];
-      if (cache_dst) reinterpret_cast<float2*>(cache_dst)[i] = v;
-    }
-    px0[p] = v.x;
-    py0[p] = v.y;
-  }
-  float tmp0 = bx, tmp1 = by, tmp2 = bth;
-#pragma unroll
-  for (int q = 0; q < 9; q++) H[q] = 0.0f;
-  int flip = 0;
-  for (int L = lv.n_levels - 1; L >= 0; --L) {
-    if (n == 0) continue;
-    const float* __restrict__ lo = lv.logodds[L];
-    const int sx = lv.sx[L], sy = lv.sy[L];
-    const float sc = lv.scale[L];
-    const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
-    const int iters = 1 + (L == 0 ? 5 : 3);
-    float e0 = (sc * tmp0 + 0.0f * tmp1) + lv.t_x[L];  // getMapCoordsPose (GridMapBase.h:238-242)
-    float e1 = (0.0f * tmp0 + sc * tmp1) + lv.t_y[L];
-    float e2 = tmp2;
-    const float lim_x = (float)sx - 2.0f, lim_y = (float)sy - 2.0f;  // MapDimensionProperties.h:66-70
-    float px[PMAX], py[PMAX];
-#pragma unroll
-    for (int p = 0; p < PMAX; p++) {
-      px[p] = px0[p] * factor;
-      py[p] = py0[p] * factor;
-    }
-    for (int it = 0; it < iters; it++) {
-      float s, c;
-      gn_sincos(e2, &s, &c);
-      int idx[PMAX];
-      float fx[PMAX], fy[PMAX];
-      bool inb[PMAX];
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        const float cx = (c * px[p] + (-s) * py[p]) + e0;
-        const float cy = (s * px[p] + c * py[p]) + e1;
-        inb[p] = have[p] && !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
-        const int ix = inb[p] ? (int)cx : 0, iy = inb[p] ? (int)cy : 0;
-        fx[p] = cx - (float)ix;
-        fy[p] = cy - (float)iy;
-        idx[p] = iy * sx + ix;
-      }
-      float l0[PMAX], l1[PMAX], l2[PMAX], l3[PMAX];
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        l0[p] = lo[idx[p]];
-        l1[p] = lo[idx[p] + 1];
-        l2[p] = lo[idx[p] + sx];
-        l3[p] = lo[idx[p] + sx + 1];
-      }
-      float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int p = 0; p < PMAX; p++) {
-        const float i0 = gn_prob_f(l0[p]), i1 = gn_prob_f(l1[p]), i2 = gn_prob_f(l2[p]), i3 = gn_prob_f(l3[p]);
-        const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;
-        const float xi = 1.0f - fx[p], yi = 1.0f - fy[p];
-        const float v = inb[p] ? ((i0 * xi + i1 * fx[p]) * (yi)) + ((i2 * xi + i3 * fx[p]) * (fy[p])) : 0.0f;
-        const float gxv = inb[p] ? -((dx1 * yi) + (dx2 * fy[p])) : 0.0f;
-        const float gyv = inb[p] ? -((dy1 * xi) + (dy2 * fx[p])) : 0.0f;
-        const float funVal = have[p] ? 1.0f - v : 0.0f;
-        const float rotDeriv = ((-s * px[p] - c * py[p]) * gxv + (c * px[p] - s * py[p]) * gyv);
-        acc[0] += gxv * funVal; acc[1] += gyv * funVal; acc[2] += rotDeriv * funVal;
-        acc[3] += gxv * gxv; acc[4] += gyv * gyv; acc[5] += rotDeriv * rotDeriv;
-        acc[6] += gxv * gyv; acc[7] += gxv * rotDeriv; acc[8] += gyv * rotDeriv;
-      }
-      gn_wave_sums9(acc);
-      if (lane == 63) {
-#pragma unroll
-        for (int q = 0; q < 9; q++) s_part[flip][wv][q] = acc[q];
-      }
-      __syncthreads();
-      float mine = 0.0f;
-      if (lane < 9) {
-        mine = s_part[flip][0][lane];
-#pragma unroll
-        for (int w = 1; w < NW; w++) mine += s_part[flip][w][lane];
-      }
-      float sum[9];
-#pragma unroll
-      for (int q = 0; q < 9; q++) sum[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), q));
-      flip ^= 1;  // the next iteration writes the other buffer: one barrier per iteration
-      gn_solve_step(sum, H, e0, e1, e2);
-    }
-    {
-      // util::normalize_angle (UtilFunctions.h:36-48), double arithmetic with M_PI
-      const double two_pi = 2.0f * 3.14159265358979323846;
-      float a = (float)fmod(fmod((double)e2, two_pi) + two_pi, two_pi);
-      if ((double)a > 3.14159265358979323846) a = (float)((double)a - two_pi);
-      // getWorldCoordsPose: worldTmap = mapTworld.inverse() (GridMapBase.h:229-233, 285)
-      const float invdet = 1.0f / (sc * sc - 0.0f * 0.0f);
-      const float l00 = sc * invdet, l01 = -0.0f * invdet, l10 = -0.0f * invdet, l11 = sc * invdet;
-      const float wt0 = -(l00 * lv.t_x[L] + l01 * lv.t_y[L]), wt1 = -(l10 * lv.t_x[L] + l11 * lv.t_y[L]);
-      tmp0 = (l00 * e0 + l01 * e1) + wt0;
-      tmp1 = (l10 * e0 + l11 * e1) + wt1;
-      tmp2 = a;
-    }
-  }
-  pose[0] = tmp0; pose[1] = tmp1; pose[2] = tmp2;
 }
 
 // last phase of a streamed match, ONE thread: state, record, gate, geometry (HectorSlamProcessor.h:98-107 + update_impl)
@@ -1623,7 +1344,7 @@ k_hs_match_reg(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int*
   float b[3], pose[3], H[9];
   const int n = hs_begin(sc, n_src, st, b);
   if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
-  else hs_match_reg_body<NT, PMAX>(lv, pts, cache_dst, n, b[0], b[1], b[2], pose, H);
+  else gn_match_reg_body<NT, PMAX>(lv, pts, cache_dst, n, b[0], b[1], b[2], pose, H);
   if (threadIdx.x == 0) hs_finish(lv, sc, st, rec, pose, H, n);
 }
 
@@ -1634,7 +1355,7 @@ k_hs_match_fast(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int
   float b[3], pose[3], H[9];
   const int n = hs_begin(sc, n_src, st, b);
   if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
-  else hs_match_fast_body<NT>(lv, pts, cache_dst, n, pts_in_lds, b[0], b[1], b[2], pose, H);
+  else gn_match_fast_body<NT>(lv, pts, cache_dst, n, pts_in_lds, b[0], b[1], b[2], pose, H);
   if (threadIdx.x == 0) hs_finish(lv, sc, st, rec, pose, H, n);
 }
 
@@ -2583,6 +2304,43 @@ int lslam_map_update_just_once(lslam_map* map, const float* pts, int n, const fl
 }
 
 namespace {
+GnLevels gn_levels_of(const lslam_map* map) {  // the pyramid as the matcher's kernels take it
+  GnLevels lv;
+  lv.n_levels = (int)map->levels.size();
+  for (int i = 0; i < lv.n_levels; i++) {
+    const Level& L = map->levels[i];
+    lv.sx[i] = L.sx; lv.sy[i] = L.sy; lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
+    lv.logodds[i] = L.d_logodds;
+  }
+  return lv;
+}
+
+// The form a parallel-sums match of up to `n` points is launched in: threads per block from LSLAM_GN_THREADS; the points of
+// the scan in registers when they fit (3 per thread at 512 threads: a 1081-beam scan), else staged in LDS, else read from memory
+struct GnForm {
+  int nt;      // 256 | 512 | 1024
+  bool reg;    // k_*_match_reg<nt, points per thread>; else k_*_match_fast<nt>
+  int in_lds;  // staged form: the points fit in LDS
+  size_t lds;  // staged form: dynamic LDS bytes (0 for the register form)
+};
+GnForm gn_form_of(const lslam_map* map, int n) {
+  GnForm f;
+  f.nt = map->gn_threads >= 1024 ? 1024 : (map->gn_threads >= 512 ? 512 : 256);
+  f.reg = n <= (f.nt == 1024 ? 1024 * 2 : (f.nt == 512 ? 512 * 3 : 256 * 5));
+  f.in_lds = (size_t)2 * n * sizeof(float) <= 56 * 1024;
+  f.lds = !f.reg && f.in_lds ? (size_t)2 * std::max(n, 1) * sizeof(float) : 0;
+  return f;
+}
+// the one ladder over the forms: REG(NT, PMAX) / FAST(NT) are the caller's launch statements
+#define LSLAM_GN_DISPATCH(F, REG, FAST)                                                                                    \
+  do {                                                                                                                     \
+    if ((F).reg) {                                                                                                         \
+      if ((F).nt == 1024) REG(1024, 2); else if ((F).nt == 512) REG(512, 3); else REG(256, 5);                             \
+    } else {                                                                                                               \
+      if ((F).nt == 1024) FAST(1024); else if ((F).nt == 512) FAST(512); else FAST(256);                                   \
+    }                                                                                                                      \
+  } while (0)
+
 int match_data_impl(lslam_map* map, const float* pts, int n, bool pts_on_device, const float origo[2],
                     const float begin_world[3], float out_pose[3], float out_cov[9]) {
   lslam_context* ctx = map->ctx;
@@ -2604,13 +2362,7 @@ int match_data_impl(lslam_map* map, const float* pts, int n, bool pts_on_device,
     map->cached_origo[0] = origo ? origo[0] : 0.f;
     map->cached_origo[1] = origo ? origo[1] : 0.f;
   }
-  GnLevels lv;
-  lv.n_levels = (int)map->levels.size();
-  for (int i = 0; i < lv.n_levels; i++) {
-    const Level& L = map->levels[i];
-    lv.sx[i] = L.sx; lv.sy[i] = L.sy; lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
-    lv.logodds[i] = L.d_logodds;
-  }
+  const GnLevels lv = gn_levels_of(map);
   if (!map->ordered_sums) {
     // ---- parallel sums (default): one launch, no copy operation on the stream --------------------------------------------
     if (!map->h_gn_out && hipHostMalloc((void**)&map->h_gn_out, 16 * sizeof(float), hipHostMallocDefault) != hipSuccess) {
@@ -2635,23 +2387,16 @@ int match_data_impl(lslam_map* map, const float* pts, int n, bool pts_on_device,
       src = map->h_gn_pts;
       map->gn_host_n = n;
     }
-    const int in_lds = (size_t)2 * n * sizeof(float) <= 56 * 1024;
-    const size_t lds = in_lds ? (size_t)2 * std::max(n, 1) * sizeof(float) : 0;
+    const GnForm form = gn_form_of(map, n);
     float* cache_dst = n > 0 ? map->d_cached.p : (float*)nullptr;
     const int ticket = ++map->gn_ticket;
 #define LSLAM_GN_FAST(NT)                                                                                                  \
-  launch(ctx, "gn_match", k_gn_match_fast<NT>, dim3(1), dim3(NT), lds, lv, src, cache_dst, n, in_lds, begin_world[0],      \
-         begin_world[1], begin_world[2], map->h_gn_out, ticket)
+  launch(ctx, "gn_match", k_gn_match_fast<NT>, dim3(1), dim3(NT), form.lds, lv, src, cache_dst, n, form.in_lds,            \
+         begin_world[0], begin_world[1], begin_world[2], map->h_gn_out, ticket)
 #define LSLAM_GN_REG(NT, PMAX)                                                                                             \
-  launch(ctx, "gn_match", k_gn_match_reg<NT, PMAX>, dim3(1), dim3(NT), 0, lv, src, cache_dst, n, begin_world[0],           \
+  launch(ctx, "gn_match", k_gn_match_reg<NT, PMAX>, dim3(1), dim3(NT), form.lds, lv, src, cache_dst, n, begin_world[0],    \
          begin_world[1], begin_world[2], map->h_gn_out, ticket)
-    // the points of the scan in registers when they fit (3 per thread at 512 threads: a 1081-beam scan), else LDS / memory
-    if (map->gn_threads >= 1024 && n <= 1024 * 2) LSLAM_GN_REG(1024, 2);
-    else if (map->gn_threads >= 512 && map->gn_threads < 1024 && n <= 512 * 3) LSLAM_GN_REG(512, 3);
-    else if (map->gn_threads < 512 && n <= 256 * 5) LSLAM_GN_REG(256, 5);
-    else if (map->gn_threads >= 1024) LSLAM_GN_FAST(1024);
-    else if (map->gn_threads >= 512) LSLAM_GN_FAST(512);
-    else LSLAM_GN_FAST(256);
+    LSLAM_GN_DISPATCH(form, LSLAM_GN_REG, LSLAM_GN_FAST);
 #undef LSLAM_GN_REG
 #undef LSLAM_GN_FAST
     LSLAM_HIP(ctx, hipGetLastError());
@@ -2751,13 +2496,7 @@ int match_batch_launch(lslam_map* map, int n_entries, int n_containers, const fl
   LSLAM_HIP(ctx, map->d_gnb_ent.reserve((size_t)n_entries));
   // (pageable source: the runtime has staged it when the call returns, like the batched update's scan headers)
   LSLAM_HIP(ctx, hipMemcpyAsync(map->d_gnb_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-  GnLevels lv;
-  lv.n_levels = (int)map->levels.size();
-  for (int i = 0; i < lv.n_levels; i++) {
-    const Level& L = map->levels[i];
-    lv.sx[i] = L.sx; lv.sy[i] = L.sy; lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
-    lv.logodds[i] = L.d_logodds;
-  }
+  const GnLevels lv = gn_levels_of(map);
   const int2* d_ent = map->d_gnb_ent.p;
   if (map->ordered_sums) {
     const size_t lds = (size_t)std::max(n_max, 1) * 9 * sizeof(float);
@@ -3006,16 +2745,14 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   h->mirror.updated = 0;
   memcpy(h->h_io, &h->mirror, kHsPersistWords * 4);
   LSLAM_HIP(ctx, hipMemcpyAsync(h->d_state, h->h_io, kHsPersistWords * 4, hipMemcpyHostToDevice, ctx->stream));
-  GnLevels lv;
+  const GnLevels lv = gn_levels_of(map);
   HsLevels ul;
-  lv.n_levels = ul.n_levels = n_levels;
+  ul.n_levels = n_levels;
   ul.lo_free = map->lo_free;
   ul.lo_occ = map->lo_occ;
   for (int i = 0; i < n_levels; i++) {
     const Level& L = map->levels[i];
-    lv.sx[i] = ul.sx[i] = L.sx; lv.sy[i] = ul.sy[i] = L.sy;
-    lv.scale[i] = L.scale_to_map; lv.t_x[i] = L.t_x; lv.t_y[i] = L.t_y;
-    lv.logodds[i] = L.d_logodds;
+    ul.sx[i] = L.sx; ul.sy[i] = L.sy;
     ul.free_key[i] = L.d_free; ul.occ_key[i] = L.d_occ; ul.logodds[i] = L.d_logodds;
   }
   int* const d_n_live = &h->d_state->n_live;
@@ -3032,10 +2769,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     for (int k = 0; k < c.n_scans; k++) first[k + 1] = first[k] + (size_t)c.n_points[k];
   }
   // the matcher's form from the CAPACITY (the live count is the device's): as match_data_impl chooses from n
-  const int nt = map->gn_threads >= 1024 ? 1024 : (map->gn_threads >= 512 ? 512 : 256);
-  const bool reg = c.capacity <= (nt == 1024 ? 1024 * 2 : (nt == 512 ? 512 * 3 : 256 * 5));
-  const int in_lds = (size_t)2 * c.capacity * sizeof(float) <= 56 * 1024;
-  const size_t lds = !reg && in_lds ? (size_t)2 * std::max(c.capacity, 1) * sizeof(float) : 0;
+  const GnForm form = gn_form_of(map, c.capacity);
   const dim3 ugrid((unsigned)((cache_cap + 3) / 4), (unsigned)n_levels), ublock(256);
   for (int k = 0; k < c.n_scans; k++) {
     HsScan sc{};
@@ -3074,18 +2808,11 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     }
     lslam_hector_record* rec = h->d_rec.p + k;
 #define LSLAM_HS_REG(NT, PMAX) \
-  launch(ctx, "hs_match", k_hs_match_reg<NT, PMAX>, dim3(1), dim3(NT), 0, lv, sc, pts, n_src, map->d_cached.p, h->d_state, rec)
-#define LSLAM_HS_FAST(NT) \
-  launch(ctx, "hs_match", k_hs_match_fast<NT>, dim3(1), dim3(NT), lds, lv, sc, pts, n_src, map->d_cached.p, in_lds, h->d_state, rec)
-    if (reg) {
-      if (nt == 1024) LSLAM_HS_REG(1024, 2);
-      else if (nt == 512) LSLAM_HS_REG(512, 3);
-      else LSLAM_HS_REG(256, 5);
-    } else {
-      if (nt == 1024) LSLAM_HS_FAST(1024);
-      else if (nt == 512) LSLAM_HS_FAST(512);
-      else LSLAM_HS_FAST(256);
-    }
+  launch(ctx, "hs_match", k_hs_match_reg<NT, PMAX>, dim3(1), dim3(NT), form.lds, lv, sc, pts, n_src, map->d_cached.p, h->d_state, rec)
+#define LSLAM_HS_FAST(NT)                                                                                                    \
+  launch(ctx, "hs_match", k_hs_match_fast<NT>, dim3(1), dim3(NT), form.lds, lv, sc, pts, n_src, map->d_cached.p, form.in_lds, \
+         h->d_state, rec)
+    LSLAM_GN_DISPATCH(form, LSLAM_HS_REG, LSLAM_HS_FAST);
 #undef LSLAM_HS_REG
 #undef LSLAM_HS_FAST
     launch(ctx, "hs_mark", k_hs_mark, ugrid, ublock, 0, ul, (const HsState*)h->d_state, pts, (const float*)map->d_cached.p);

@@ -8,6 +8,7 @@ import pytest
 
 from lslam_amd import api
 
+import gn_edge_cases as E
 import hector_stream_cases as S
 
 pytestmark = pytest.mark.gpu
@@ -247,6 +248,36 @@ def test_interop_with_the_host_driven_calls(po, ctx):
         h.process_many_points(sc.containers[:1])
     assert e.value.code == -8  # LSLAM_ERR_UNSUPPORTED
     m.close()
+
+
+@pytest.fixture(scope="module")
+def gn_maps(ctx):
+    """The smallest map of tests/gn_edge_cases.py's geometries, built once under each LSLAM_GN_THREADS."""
+    case = E.geometry_case("256x192")
+    with pytest.MonkeyPatch.context() as mp:
+        dev = E.DeviceMaps(ctx, api, mp, case)
+    yield case, dev
+    for m in dev.maps.values():
+        m.close()
+
+
+@pytest.mark.parametrize("form", ["reg256", "reg512", "reg1024", "fast-lds", "fast-mem"])
+def test_streamed_match_is_match_data_bit_for_bit(gn_maps, form):
+    """9. The streamed match IS lslam_map_match_data: one container and start pose through matchData and then, on the same
+    map, through a streamed call of one scan with that pose as its hint (the call's capacity is the container's size, so
+    both launch the same form; matchData changes no plane, so both see the same map).  The record's 3 pose words and 9
+    covariance words equal matchData's, as uint32."""
+    case, dev = gn_maps
+    pts, begin = case.containers[E.FORM_CONTAINER[form]], case.begin[E.FORM_CONTAINER[form]]
+    pose, H = dev.match(form, pts, begin)
+    # the streamed scan passes the gate and updates the shared map AFTER its match: the next form's pair sees that map, both halves
+    h = api.HectorProcessor(dev.maps[E.SINGLE_FORMS[form][0]])
+    rec = h.process_many_points([pts], pose_hints=[begin])[0]
+    h.close()
+    assert rec["n_points"] == len(pts)
+    got = np.concatenate([rec["pose"].ravel(), rec["cov"].ravel()]).view(np.uint32)
+    want = np.concatenate([np.asarray(pose, f32).ravel(), np.asarray(H, f32).ravel()]).view(np.uint32)
+    assert np.array_equal(got, want), (form, len(pts), got, want)
 
 
 def test_what_the_kernels_cannot_take_is_refused(ctx):
