@@ -359,6 +359,7 @@ def lib() -> C.CDLL:
     L.lslam_matcher_step_kernel_launches.restype = C.c_int64
     L.lslam_matcher_lone_kernel_launches.argtypes = [vp]
     L.lslam_matcher_lone_kernel_launches.restype = C.c_int64
+    L.lslam_matcher_coarse_form_launches.argtypes = [vp, vp]
     i64 = C.c_int64
     L.lslam_scan_cache_create.argtypes = [vp, C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_scan_cache_destroy.argtypes = [vp]
@@ -498,6 +499,13 @@ class Context:
         return {buf[i].name.decode(): (int(buf[i].launches), float(buf[i].total_ms)) for i in range(n)}
 
 
+MATCHER_OPTIONS = {"row_occupancy": 1, "collect_stats": 2, "lds_staged": 3, "pipeline_depth": 4, "step_kernel": 5,
+                   "step_min_scans": 6, "rows_waves": 7, "check_output_reuse": 8, "lone_kernel": 9}  # LSLAM_OPT_*
+# LSLAM_FORM_* in the header's order
+COARSE_FORMS = ("generic", "rows_linear", "rows_tiled", "rows_multiwave", "rows_lds_staged", "rows_stats_linear",
+                "rows_stats_tiled", "rows_stats_lds_staged", "big", "fine_rows", "fine_tile3")
+
+
 class ScanMatcher:
     """karto::ScanMatcher on the GPU.  Poses are SENSOR poses (x, y, heading)."""
 
@@ -574,9 +582,7 @@ class ScanMatcher:
         self.ctx.check(self.L.lslam_matcher_set_grid_u8_dev(self.h, ptr, o.ctypes.data))
 
     def set_option(self, name: str, value: int):
-        opt = {"row_occupancy": 1, "collect_stats": 2, "lds_staged": 3, "pipeline_depth": 4, "step_kernel": 5,
-               "step_min_scans": 6, "rows_waves": 7, "check_output_reuse": 8, "lone_kernel": 9}[name]
-        self.ctx.check(self.L.lslam_matcher_set_option(self.h, opt, int(value)))
+        self.ctx.check(self.L.lslam_matcher_set_option(self.h, MATCHER_OPTIONS[name], int(value)))
 
     @property
     def step_kernel_launches(self) -> int:
@@ -587,6 +593,20 @@ class ScanMatcher:
     def lone_kernel_launches(self) -> int:
         """Single-scan matches that went out as ONE launch (set_option('lone_kernel', 4 / 8 / 16)) so far."""
         return int(self.L.lslam_matcher_lone_kernel_launches(self.h))
+
+    def coarse_form_launches(self) -> dict:
+        """Response-kernel launches so far, per form (lslam_matcher_coarse_form_launches): every coarse form goes out
+        under the one profile name 'resp_rows_coarse', so this is how a caller that selected a form with set_option sees
+        that it -- and not a fallback -- ran."""
+        out = (C.c_int64 * len(COARSE_FORMS))()
+        self.ctx.check(self.L.lslam_matcher_coarse_form_launches(self.h, out))
+        return {name: int(out[i]) for i, name in enumerate(COARSE_FORMS)}
+
+    def get_option(self, name: str) -> int:
+        v = int(self.L.lslam_matcher_get_option(self.h, MATCHER_OPTIONS[name]))
+        if v < 0:
+            raise LslamError(v, "lslam_matcher_get_option(%s)" % name)
+        return v
 
     def flush(self):
         """Order the context stream behind every pipelined step in flight (set_option('pipeline_depth', D > 1))."""

@@ -3597,6 +3597,7 @@ struct lslam_matcher {
   int step_waves = 0;               // lslam_matcher_set_option(LSLAM_OPT_STEP_KERNEL): 0 = five launches per step, 3 / 4 = k_match_step with that many waves per scan
   int step_min_scans = 64;          // batches below this keep the five-kernel path (its beam-sliced kernels fill the chip)
   uint64_t step_launches = 0;       // k_match_step launches so far (diagnostics / tests)
+  int64_t form_launches[LSLAM_FORM_COUNT] = {};  // response-kernel launches per form (lslam_matcher_coarse_form_launches); host only
   int stats_scans = 0;              // scans the per-(scan, beam) flag words behind the counters are sized for
   DevBuf<unsigned long long> d_stats;
   uint32_t* d_occ_t = nullptr;      // transposed row-occupancy bitmap (k_row_occupancy)
@@ -3951,6 +3952,7 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
     bool tiled = variant == 1 && step == 1 && p.nx == 3 && p.ny == 3 && waves >= kTileMinWaves && tiles4_possible();
     if (tiled) tiled = ensure_tiles4();
     if (tiled) {
+      m->form_launches[LSLAM_FORM_FINE_TILE3]++;
 #define LSLAM_TILE3_ARGS                                                                                                \
   (const uint4*)m->d_tiles, m->tile_cols, g, p, (const Lattice*)m->d_lat.p, (const double2*)m->d_cossin.p,              \
       (const double2*)m->d_local.p, m->d_resp.p, resp_stride, S
@@ -4000,24 +4002,30 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
         LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
         m->stats_scans = S;
       }
+      int form;  // which of the forms below takes this pass (host-side count: lslam_matcher_coarse_form_launches)
       if (m->lds_staged && variant == 2 && step == 2) {  // experiment (DESIGN_HISTORY.md B): phase B through LDS patches
+        form = m->collect_stats ? LSLAM_FORM_ROWS_STATS_LDS_STAGED : LSLAM_FORM_ROWS_LDS_STAGED;
         if (m->collect_stats)
           launch(ctx, name, k_resp_rows<3, 11, false, true, true>, LSLAM_ROWS_ARGS(s0, s1));
         else
           launch(ctx, name, k_resp_rows<3, 11, false, false, true>, LSLAM_ROWS_ARGS(s0, s1));
       } else if (m->collect_stats && variant == 2 && step == 2) {  // instrumented twin (untimed diagnostics only)
+        form = ptiled ? LSLAM_FORM_ROWS_STATS_TILED : LSLAM_FORM_ROWS_STATS_LINEAR;
         if (ptiled)
           launch(ctx, name, k_resp_rows<3, 11, true, true>, LSLAM_ROWS_ARGS(pt, pt));
         else
           launch(ctx, name, k_resp_rows<3, 11, false, true>, LSLAM_ROWS_ARGS(s0, s1));
       } else if (m->collect_stats && variant == 3 && step == 2) {  // the same for lattice rows of 13..16 positions
+        form = ptiled ? LSLAM_FORM_ROWS_STATS_TILED : LSLAM_FORM_ROWS_STATS_LINEAR;
         if (ptiled)
           launch(ctx, name, k_resp_rows<4, 8, true, true>, LSLAM_ROWS_ARGS(pt, pt));
         else
           launch(ctx, name, k_resp_rows<4, 8, false, true>, LSLAM_ROWS_ARGS(s0, s1));
-      } else if (variant == 1)
+      } else if (variant == 1) {
+        form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
         launch(ctx, name, k_resp_rows<1, 4, false>, LSLAM_ROWS_ARGS(s0, s1));
-      else if ((variant == 2 || variant == 3) && ptiled && m->rows_waves > 1 && g.n_beams <= 64 * kMaxBeamsPerLane) {
+      } else if ((variant == 2 || variant == 3) && ptiled && m->rows_waves > 1 && g.n_beams <= 64 * kMaxBeamsPerLane) {
+        form = LSLAM_FORM_ROWS_MULTIWAVE;
         const int W = m->rows_waves, groups = (p.na + W - 1) / W;
         const dim3 mw_grid((unsigned)((long long)((S + 7) / 8) * 8 * groups));
 #define LSLAM_MW(NXD_, NYC_, W_)                                                                                         \
@@ -4031,16 +4039,23 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
         else if (variant == 3 && W == 4) LSLAM_MW(4, 8, 4);
         else LSLAM_MW(4, 8, 8);
 #undef LSLAM_MW
-      } else if (variant == 2 && ptiled)
+      } else if (variant == 2 && ptiled) {
+        form = LSLAM_FORM_ROWS_TILED;
         launch(ctx, name, k_resp_rows<3, 11, true>, LSLAM_ROWS_ARGS(pt, pt));
-      else if (variant == 2)
+      } else if (variant == 2) {
+        form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
         launch(ctx, name, k_resp_rows<3, 11, false>, LSLAM_ROWS_ARGS(s0, s1));
-      else if (ptiled)
+      } else if (ptiled) {
+        form = LSLAM_FORM_ROWS_TILED;
         launch(ctx, name, k_resp_rows<4, 8, true>, LSLAM_ROWS_ARGS(pt, pt));
-      else
+      } else {
+        form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
         launch(ctx, name, k_resp_rows<4, 8, false>, LSLAM_ROWS_ARGS(s0, s1));
+      }
+      m->form_launches[form]++;
 #undef LSLAM_ROWS_ARGS
     } else {
+      m->form_launches[LSLAM_FORM_GENERIC]++;
       int chunks = (p.nx * p.ny + kPosChunk - 1) / kPosChunk;
       long long items = (long long)S * p.na * chunks;
       launch(ctx, "resp_generic", k_resp_generic, dim3((unsigned)std::min<long long>(items, 1 << 20)), dim3(64), 0,
@@ -4078,6 +4093,7 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
     constexpr int max_slices = 8;  // = kMaxSlices of k_big_latmax
     while (slices < max_slices && (long long)S * p.na * n_tiles * slices < 1024) slices *= 2;
     if (slices > 1) LSLAM_HIP(ctx, m->d_part.reserve((size_t)S * slices * resp_stride));
+    m->form_launches[LSLAM_FORM_BIG]++;
     if (lone)
       launch(ctx, "resp_dense", k_resp_dense<1>, dim3((unsigned)((long long)S * p.na * n_tiles * slices)), dim3(64), 0,
              (const uint8_t*)m->d_sub[0], (const uint8_t*)m->d_sub[1], g.data_size / 2, g, p, (const Lattice*)m->d_lat.p,
@@ -4879,6 +4895,11 @@ int lslam_matcher_flush(lslam_matcher* m) {
 int64_t lslam_matcher_pipelined_steps(const lslam_matcher* m) { return m ? (int64_t)m->pipe_steps : 0; }
 int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->step_launches : 0; }
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->lone_launches : 0; }
+int lslam_matcher_coarse_form_launches(const lslam_matcher* m, int64_t out[LSLAM_FORM_COUNT]) {
+  if (!m || !out) return LSLAM_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < LSLAM_FORM_COUNT; i++) out[i] = m->form_launches[i];
+  return LSLAM_OK;
+}
 // diagnostics: the hand-over words of k_match_lone (kLoneRing slots of 8 words) after a stream sync
 int lslam_debug_lone_sync(lslam_matcher* m, unsigned* out128) {
   if (!m || !out128) return LSLAM_ERR_INVALID_ARGUMENT;

@@ -157,7 +157,10 @@ void* lslam_matcher_grid_dev_ptr(lslam_matcher* m);
  *  LSLAM_OPT_COLLECT_STATS (default 0): 1 clears the counters and routes coarse passes through an instrumented twin of
  *    the hot kernel (slower: for an untimed diagnostic launch); lslam_matcher_read_stats then returns, summed over
  *    the passes since: [0] lattice rows inside the reference's index range (Mapper.cpp:841-845), [1] rows still live
- *    after pruning, [2] readable beam x angle pairs, [3] those with at least one live row. */
+ *    after pruning, [2] readable beam x angle pairs, [3] those with at least one live row.  The kernel takes a lattice in
+ *    blocks of 11 rows (lattice rows of up to 12 positions) or 8 rows (13..16 positions) and visits every beam once per
+ *    block: on a lattice with more rows than one block holds, [2] and [3] count beam x angle x row-block triples
+ *    (16 x 16 x 21: every readable pair twice in [2]; in [3] once per block in which it has a live row). */
 /*  LSLAM_OPT_LDS_STAGED (default 0): 1 routes the coarse pass of chip-filling batches through the LDS-staged variant of
  *    the hot kernel (phase B reads its rows from per-drain patches of the parity planes staged in LDS): an experiment that
  *    was measured and dropped (DESIGN_HISTORY.md B, "LDS-staged experiment"), kept selectable so the measurement can be repeated. */
@@ -210,6 +213,25 @@ int64_t lslam_matcher_pipelined_steps(const lslam_matcher* m);
 int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m);
 /* diagnostics: single-scan matches that went out as ONE launch (LSLAM_OPT_LONE_KERNEL) so far */
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m);
+/* diagnostics: which FORM of the response kernel took the passes of the matches so far.  Every coarse form goes out under
+ * the same profile name (resp_rows_coarse), and the dispatch falls back silently (a batch below the tiled planes' threshold,
+ * more than 2048 beams, planes that could not be allocated ...): a test or an A/B run that selects a form with
+ * lslam_matcher_set_option reads here whether that form really ran.  One count per launch, kept on the host (no device cost);
+ * matches that went out as ONE kernel (LSLAM_OPT_STEP_KERNEL / LSLAM_OPT_LONE_KERNEL) are counted by the two functions above
+ * instead.  Coarse passes (expansion passes included):
+ *   GENERIC                k_resp_generic: a lattice outside the packed kernels, or forced (either pass)
+ *   ROWS_LINEAR            k_resp_rows on the linear parity planes (small batches: beam slices)
+ *   ROWS_TILED             k_resp_rows on the tiled parity planes (chip-filling batches; the hot kernel)
+ *   ROWS_MULTIWAVE         k_resp_rows_mw (LSLAM_OPT_ROWS_WAVES 2 / 4 / 8)
+ *   ROWS_LDS_STAGED        k_resp_rows, phase B through LDS patches of the linear planes (LSLAM_OPT_LDS_STAGED)
+ *   ROWS_STATS_LINEAR / ROWS_STATS_TILED / ROWS_STATS_LDS_STAGED   the instrumented twins (LSLAM_OPT_COLLECT_STATS) of the three
+ *   BIG                    k_resp_dense (loop-closure-size lattices)
+ * and the fine pass: FINE_ROWS (k_resp_rows on the grid itself), FINE_TILE3 (k_resp_tile3 on the 4x4 blocks). */
+enum { LSLAM_FORM_GENERIC = 0, LSLAM_FORM_ROWS_LINEAR = 1, LSLAM_FORM_ROWS_TILED = 2, LSLAM_FORM_ROWS_MULTIWAVE = 3,
+       LSLAM_FORM_ROWS_LDS_STAGED = 4, LSLAM_FORM_ROWS_STATS_LINEAR = 5, LSLAM_FORM_ROWS_STATS_TILED = 6,
+       LSLAM_FORM_ROWS_STATS_LDS_STAGED = 7, LSLAM_FORM_BIG = 8, LSLAM_FORM_FINE_ROWS = 9, LSLAM_FORM_FINE_TILE3 = 10,
+       LSLAM_FORM_COUNT = 11 };
+int lslam_matcher_coarse_form_launches(const lslam_matcher* m, int64_t out[LSLAM_FORM_COUNT]);
 /* diagnostics: k_match_lone's hand-over words, 16 slots x 8 words {coarse tickets, coarse done, fine ready, fine tickets,
  * fine done, timeouts, 0, 0}; LSLAM_ERR_NO_DATA before the first such launch */
 int lslam_debug_lone_sync(lslam_matcher* m, unsigned* out128);

@@ -25,6 +25,22 @@ def test_header_symbols_are_exported():
     assert not missing, missing
 
 
+def test_coarse_form_counter_is_declared_and_exported():
+    """lslam_matcher_coarse_form_launches: in the header with one LSLAM_FORM_* per name the Python binding reports, exported
+    by the built library, and refusing a null handle -- no device needed."""
+    header = (ROOT / "include" / "lslam_gpu.h").read_text()
+    assert re.search(r"\bint\s+lslam_matcher_coarse_form_launches\s*\(\s*const\s+lslam_matcher\s*\*", header)
+    forms = dict(re.findall(r"\bLSLAM_FORM_([A-Z0-9_]+)\s*=\s*(\d+)", header))
+    count = int(forms.pop("COUNT"))
+    assert sorted(int(v) for v in forms.values()) == list(range(count))
+    assert tuple(k.lower() for k, _ in sorted(forms.items(), key=lambda kv: int(kv[1]))) == api.COARSE_FORMS
+    L = api.lib()
+    assert hasattr(L, "lslam_matcher_coarse_form_launches")
+    out = (ctypes.c_int64 * count)()
+    assert L.lslam_matcher_coarse_form_launches(None, out) == -1  # LSLAM_ERR_INVALID_ARGUMENT
+    assert L.lslam_abi_version() == 5
+
+
 def test_abi_version_and_struct_sizes():
     L = api.lib()
     assert L.lslam_abi_version() == 5

@@ -161,6 +161,20 @@ def test_coarse_sums_of_whole_batches_bit_exact(ctx, oracle_lib, workload_spread
     assert n_fine >= len(check) // 2
 
 
+def half_cell_boundary_scan(laser):
+    """Ranges that put EVERY beam's scan-frame x or y on (k + 0.5 +- 3e-7) cells of a 0.05 m grid (see
+    test_beams_on_half_cell_boundaries; shared with test_coarse_variants_gpu.py)."""
+    n = laser.n_ranges
+    phi = laser.angle_min + np.arange(n) * laser.angle_increment
+    b = np.arange(n)
+    on_x = np.abs(np.cos(phi)) > 0.6
+    off = np.where(b % 2 == 0, 3e-7, -3e-7)  # cells: far inside the fp32 band (~1e-4), far outside libm's last-ulp noise
+    r = np.where(on_x, ((100 + b % 40) + 0.5 + off) / 20.0 / np.abs(np.cos(phi)),
+                 ((60 + b % 30) + 0.5 + off) / 20.0 / np.maximum(np.abs(np.sin(phi)), 1e-3))
+    r[::97] = np.nan  # a few INVALID_SCAN readings among them
+    return r
+
+
 @pytest.mark.parametrize("heading", [0.0, math.pi / 2])
 def test_beams_on_half_cell_boundaries(ctx, oracle_lib, heading):
     """Phase A of k_resp_rows decides a beam's table cell on an fp32 estimate and parks the beams whose coordinate lies
@@ -170,14 +184,7 @@ def test_beams_on_half_cell_boundaries(ctx, oracle_lib, heading):
     fp32), so whole waves of beams take the parked path; the numerators must still be the reference's bit for bit."""
     laser = synth.Laser()
     port, gm = make_pair(ctx, oracle_lib, laser)
-    n = laser.n_ranges
-    phi = laser.angle_min + np.arange(n) * laser.angle_increment
-    b = np.arange(n)
-    on_x = np.abs(np.cos(phi)) > 0.6
-    off = np.where(b % 2 == 0, 3e-7, -3e-7)  # cells: far inside the fp32 band (~1e-4), far outside libm's last-ulp noise
-    r = np.where(on_x, ((100 + b % 40) + 0.5 + off) / 20.0 / np.abs(np.cos(phi)),
-                 ((60 + b % 30) + 0.5 + off) / 20.0 / np.maximum(np.abs(np.sin(phi)), 1e-3))
-    r[::97] = np.nan  # a few INVALID_SCAN readings among them
+    r = half_cell_boundary_scan(laser)
     base_poses = np.array([[1.0, 2.0, heading], [1.05, 2.0, heading], [1.0, 1.95, heading]])
     base_ranges = np.stack([r, r, r])
     center = np.array([1.03, 1.98, heading])  # candidate 10 of 21: (heading - 0.349) + 10 * 0.0349 = heading (+- 1 ulp)
