@@ -166,6 +166,77 @@ def deskew_scan(ctx, ranges_f32, params: DeskewParams, imu_time=None, imu_rot=No
     return xyz, valid.astype(bool)
 
 
+def _deskew_inputs(params, imu_times, imu_rots):
+    """Per-scan params and IMU samples -> (DeskewParams array, imu_first [n+1] int32, time [T], rot [3, T] float64).
+    imu_times[k]: scan k's sample times (None or empty: no sample), imu_rots[k]: [n_k, 3]."""
+    n = len(params)
+    arr = (DeskewParams * max(n, 1))(*params)
+    counts = [0 if (imu_times is None or imu_times[k] is None) else len(imu_times[k]) for k in range(n)]
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum(counts)
+    total = int(first[-1])
+    it = np.zeros(max(total, 1), np.float64)
+    ir = np.zeros((3, max(total, 1)), np.float64)
+    for k in range(n):
+        if counts[k]:
+            it[first[k]:first[k + 1]] = np.asarray(imu_times[k], np.float64)
+            ir[:, first[k]:first[k + 1]] = np.asarray(imu_rots[k], np.float64).reshape(counts[k], 3).T
+    return arr, first, it, ir
+
+
+class Deskewer:
+    """lslam_deskew: lesson5's CorrectLaserScan for many scans of one geometry per launch.  Owns its device and pinned
+    buffers and the cached angle table; every scan's output is bit for bit deskew_scan's."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_deskew_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_deskew_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def batch(self, ranges, params, imu_times=None, imu_rots=None, n_readings=None):
+        """ranges: [n_scans, stride] float32 (n_readings <= stride beams of each row are the scan), params: a DeskewParams per
+        scan -> (xyz [n_scans, n_readings, 3] float32, valid [n_scans, n_readings] bool)."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        r = r.reshape(len(params), -1) if len(params) else r.reshape(0, r.shape[-1] if r.ndim > 1 else 0)
+        n, stride = r.shape
+        nr = stride if n_readings is None else int(n_readings)
+        arr, first, it, ir = _deskew_inputs(params, imu_times, imu_rots)
+        xyz = np.zeros((n, nr, 3), np.float32)
+        valid = np.zeros((n, nr), np.uint8)
+        self.ctx.check(self.L.lslam_deskew_batch(self.h, n, nr, r.ctypes.data, stride, C.addressof(arr), first.ctypes.data,
+                                                 it.ctypes.data, ir[0].ctypes.data, ir[1].ctypes.data, ir[2].ctypes.data,
+                                                 xyz.ctypes.data, valid.ctypes.data))
+        return xyz, valid.astype(bool)
+
+    def batch_dev(self, n_readings: int, ranges_ptr: int, ranges_stride: int, params, imu_times, imu_rots, xyz_ptr: int,
+                  valid_ptr: int):
+        """The same with ranges, xyz (float32) and valid (uint8) in HBM: asynchronous on the context's stream, no host wait."""
+        arr, first, it, ir = _deskew_inputs(params, imu_times, imu_rots)
+        self.ctx.check(self.L.lslam_deskew_batch_dev(self.h, len(params), n_readings, ranges_ptr, ranges_stride, C.addressof(arr),
+                                                     first.ctypes.data, it.ctypes.data, ir[0].ctypes.data, ir[1].ctypes.data,
+                                                     ir[2].ctypes.data, xyz_ptr, valid_ptr))
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_deskew_stats(self.h, out))
+        return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
 class GMapGeometry(C.Structure):
     _fields_ = [("map_size_x", C.c_int32), ("map_size_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("size_x2", C.c_int32), ("size_y2", C.c_int32), ("patches_x", C.c_int32), ("patches_y", C.c_int32),
@@ -349,6 +420,15 @@ def lib() -> C.CDLL:
     L.lslam_pool_set_base_scans.argtypes = [vp, i32, vp, i32, vp, vp, i32]
     L.lslam_pool_match_batch.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
     L.lslam_deskew_scan.argtypes = [vp, vp, i32, C.POINTER(DeskewParams), vp, vp, vp, vp, i32, vp, vp]
+    L.lslam_deskew_create.argtypes = [vp, C.POINTER(vp)]
+    L.lslam_deskew_destroy.argtypes = [vp]
+    L.lslam_deskew_destroy.restype = None
+    L.lslam_deskew_stats.argtypes = [vp, vp]
+    L.lslam_deskew_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_deskew_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_map_set_cloud.argtypes = [vp, vp, vp, i32, C.POINTER(HectorScan), C.POINTER(i32)]
+    L.lslam_hector_process_many_deskewed.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp]
     L.lslam_clock_sample.argtypes = [vp, vp]
     L.lslam_matcher_get_option.argtypes = [vp, i32]
     L.lslam_matcher_set_option.argtypes = [vp, i32, i32]
@@ -1224,6 +1304,16 @@ class OccGridMap:
         self.ctx.check(self.L.lslam_map_set_scan(self.h, r.ctypes.data, r.shape[0], C.byref(scan), C.byref(n)))
         return n.value
 
+    def setCloud(self, xyz, valid, scan: HectorScan) -> int:
+        """A de-skewed cloud (deskew_scan / Deskewer.batch: xyz [n,3], valid [n]) -> DataContainer on the device
+        (hector_slam.cc:320-362); returns the container size.  lesson5's cloud has z ~ 1: the z window must contain 1."""
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        v = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+        assert len(v) == len(p)
+        n = C.c_int32()
+        self.ctx.check(self.L.lslam_map_set_cloud(self.h, p.ctypes.data, v.ctypes.data, len(p), C.byref(scan), C.byref(n)))
+        return n.value
+
     def container(self):
         """-> (points [n,2] float32, origo [2]) of the resident container."""
         origo = np.zeros(2, np.float32)
@@ -1401,6 +1491,22 @@ class HectorProcessor:
         out = np.zeros(n, HECTOR_RECORD)
         self.ctx.check(self.L.lslam_hector_process_many(
             self.h, C.byref(scan), n, r.shape[1], r.ctypes.data, r.shape[1], None if hints is None else hints.ctypes.data,
+            None if flags is None else flags.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_deskewed(self, ranges, scan: HectorScan, params, imu_times=None, imu_rots=None, pose_hints=None,
+                         map_without_matching=None) -> np.ndarray:
+        """ranges: [n_scans, n_readings] RAW LaserScans + what Deskewer.batch takes -> HECTOR_RECORD[n_scans]: one batched
+        de-skew launch, then cloud -> container, match, mark and apply per scan; one host synchronisation."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        r = r.reshape(len(params), -1) if len(params) else r.reshape(0, r.shape[-1] if r.ndim > 1 else 0)
+        n = r.shape[0]
+        hints, flags = self._hints_flags(n, pose_hints, map_without_matching)
+        arr, first, it, ir = _deskew_inputs(params, imu_times, imu_rots)
+        out = np.zeros(n, HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many_deskewed(
+            self.h, C.byref(scan), n, r.shape[1], r.ctypes.data, r.shape[1], C.addressof(arr), first.ctypes.data, it.ctypes.data,
+            ir[0].ctypes.data, ir[1].ctypes.data, ir[2].ctypes.data, None if hints is None else hints.ctypes.data,
             None if flags is None else flags.ctypes.data, out.ctypes.data))
         return out
 

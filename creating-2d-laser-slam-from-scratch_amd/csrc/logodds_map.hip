@@ -615,38 +615,19 @@ struct ProjectCfg {
   float scale_to_map;
 };
 
-__global__ void __launch_bounds__(1024)
-k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* __restrict__ cossin,
-                 float* __restrict__ out_xy, int* __restrict__ out_n) {
+// Order-preserving compaction of one block of 1024: keep(i, ox, oy) says whether beam i enters and what it becomes.  Rounds
+// of 1024 beams; the count stays on the device.
+template <class Keep>
+__device__ __forceinline__ void hector_compact(int n, float* __restrict__ out_xy, int* __restrict__ out_n, Keep keep_fn) {
   __shared__ int s_wave[16];
   __shared__ int s_base;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (tid == 0) s_base = 0;
   __syncthreads();
-  for (int i0 = 0; i0 < c.n; i0 += 1024) {
+  for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + tid;
-    bool keep = false;
     float ox = 0.f, oy = 0.f;
-    if (i < c.n) {
-      const float r = ranges[i];
-      if (r < c.cutoff && r >= c.range_min) {  // laser_geometry::projectLaser_ (NaN fails both)
-        const double2 cs = cossin[i];
-        const float x = (float)((double)r * cs.x), y = (float)((double)r * cs.y);  // sensor_msgs/PointCloud: float32
-        const float d2 = x * x + y * y;                                            // hector_slam.cc:336
-        if (d2 > c.sqr_min && d2 < c.sqr_max && !(x < 0.0f && d2 < 0.50f) && !((double)d2 > c.use_max_sq)) {
-          // tf::Transform * tf::Vector3 in double (:349): row . v, then + origin
-          const double bx = (c.cy * (double)x + (-c.sy) * (double)y + 0.0 * 0.0) + c.tx;
-          const double by = (c.sy * (double)x + c.cy * (double)y + 0.0 * 0.0) + c.ty;
-          const double bz = (0.0 * (double)x + 0.0 * (double)y + 1.0 * 0.0) + c.tz;
-          const float zl = (float)(bz - c.tz);  // pointPosLaserFrameZ (:352)
-          if (zl > c.z_min && zl < c.z_max) {
-            keep = true;
-            ox = (float)bx * c.scale_to_map;  // Eigen::Vector2f(x, y) * scaleToMap (:357)
-            oy = (float)by * c.scale_to_map;
-          }
-        }
-      }
-    }
+    const bool keep = i < n && keep_fn(i, ox, oy);
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_wave[wv] = __popcll(bal);
     __syncthreads();
@@ -666,6 +647,44 @@ k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* 
     __syncthreads();
   }
   if (tid == 0) *out_n = s_base;
+}
+
+// rosPointCloudToDataContainer's loop body (hector_slam.cc:333-358) for one point of the cloud
+__device__ __forceinline__ bool hector_cloud_point(const ProjectCfg& c, float x, float y, float z, float& ox, float& oy) {
+  const float d2 = x * x + y * y;  // :335
+  if (!(d2 > c.sqr_min && d2 < c.sqr_max && !(x < 0.0f && d2 < 0.50f) && !((double)d2 > c.use_max_sq))) return false;
+  // tf::Transform * tf::Vector3 in double (:348): row . v, then + origin
+  const double bx = (c.cy * (double)x + (-c.sy) * (double)y + 0.0 * (double)z) + c.tx;
+  const double by = (c.sy * (double)x + c.cy * (double)y + 0.0 * (double)z) + c.ty;
+  const double bz = (0.0 * (double)x + 0.0 * (double)y + 1.0 * (double)z) + c.tz;
+  const float zl = (float)(bz - c.tz);  // pointPosLaserFrameZ (:351)
+  if (!(zl > c.z_min && zl < c.z_max)) return false;
+  ox = (float)bx * c.scale_to_map;  // Eigen::Vector2f(x, y) * scaleToMap (:356)
+  oy = (float)by * c.scale_to_map;
+  return true;
+}
+
+__global__ void __launch_bounds__(1024)
+k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* __restrict__ cossin,
+                 float* __restrict__ out_xy, int* __restrict__ out_n) {
+  hector_compact(c.n, out_xy, out_n, [&](int i, float& ox, float& oy) {
+    const float r = ranges[i];
+    if (!(r < c.cutoff && r >= c.range_min)) return false;  // laser_geometry::projectLaser_ (NaN fails both)
+    const double2 cs = cossin[i];
+    const float x = (float)((double)r * cs.x), y = (float)((double)r * cs.y);  // sensor_msgs/PointCloud: float32
+    return hector_cloud_point(c, x, y, 0.0f, ox, oy);                          // (projectLaser's cloud has z = 0)
+  });
+}
+
+// A de-skewed cloud (lslam_deskew_*: xyz + valid per beam) -> DataContainer: rosPointCloudToDataContainer applied to the
+// beams with valid = 1, in beam order.  ProjectCfg's range_min / cutoff are not read.
+__global__ void __launch_bounds__(1024)
+k_hector_cloud_container(ProjectCfg c, const float* __restrict__ xyz, const uint8_t* __restrict__ valid,
+                         float* __restrict__ out_xy, int* __restrict__ out_n) {
+  hector_compact(c.n, out_xy, out_n, [&](int i, float& ox, float& oy) {
+    if (!valid[i]) return false;
+    return hector_cloud_point(c, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ox, oy);
+  });
 }
 
 __global__ void k_occupancy_i8(const float* __restrict__ v, int8_t* __restrict__ out, size_t n) {
@@ -2274,6 +2293,35 @@ int lslam_map_set_scan(lslam_map* map, const float* ranges, int n, const lslam_h
   return LSLAM_OK;
 }
 
+int lslam_map_set_cloud(lslam_map* map, const float* xyz, const uint8_t* valid, int n, const lslam_hector_scan* sp, int* n_points) {
+  if (!map || n < 0 || (n > 0 && (!xyz || !valid)) || !sp) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per cloud (got %d)", kMaxBeams, n);
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n, 1) + 4));
+  // the cloud's way up shares the ranges' buffer: [xyz: 3 n floats | valid: n bytes]
+  LSLAM_HIP(ctx, map->d_scan_ranges.reserve((size_t)3 * std::max(n, 1) + ((size_t)n + 3) / 4));
+  float* d_xyz = map->d_scan_ranges.p;
+  uint8_t* d_valid = reinterpret_cast<uint8_t*>(map->d_scan_ranges.p + (size_t)3 * std::max(n, 1));
+  if (n > 0) {
+    LSLAM_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    LSLAM_HIP(ctx, hipMemcpyAsync(d_valid, valid, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const ProjectCfg c = project_cfg(map, n, sp);
+  int* d_n = reinterpret_cast<int*>(map->d_scan.p + (size_t)2 * std::max(n, 1));
+  launch(ctx, "hector_cloud_container", k_hector_cloud_container, dim3(1), dim3(1024), 0, c, (const float*)d_xyz,
+         (const uint8_t*)d_valid, map->d_scan.p, d_n);
+  int host_n = 0;
+  LSLAM_HIP(ctx, hipMemcpyAsync(&host_n, d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  map->n_scan = host_n;
+  // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:329)
+  map->scan_origo[0] = (float)(double)sp->laser_x * c.scale_to_map;
+  map->scan_origo[1] = (float)(double)sp->laser_y * c.scale_to_map;
+  if (n_points) *n_points = host_n;
+  return LSLAM_OK;
+}
+
 int lslam_map_read_container(lslam_map* map, float* out_xy, int capacity, float origo_xy[2]) {
   if (!map || capacity < 0 || (capacity > 0 && !out_xy)) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_context* ctx = map->ctx;
@@ -2665,6 +2713,10 @@ struct lslam_hector {
   DevBuf<lslam_hector_record> d_rec;
   DevBuf<float> d_ranges;
   DevBuf<int> d_counts;
+  // de-skewed form: the batched lesson5 stage in front (created with the first such call) and its cloud in HBM
+  lslam_deskew* deskew = nullptr;
+  DevBuf<float> d_xyz;
+  DevBuf<uint8_t> d_valid;
   int64_t n_scans = 0, n_updates = 0, n_calls = 0, n_syncs = 0;
 };
 
@@ -2708,6 +2760,7 @@ struct HsCall {
   int n_scans = 0, capacity = 0;
   const lslam_hector_scan* scan = nullptr;   // ranges form: project scan k's readings into the map's resident container
   int n_readings = 0;
+  bool cloud = false;                        // de-skewed form: scan k's cloud (h->d_xyz, h->d_valid) goes there instead
   const float* d_points = nullptr;           // container form: the packed points in HBM,
   const int32_t* n_points = nullptr;         //   their host counts (offsets) and
   const float* origos = nullptr;             //   origos (may be null)
@@ -2795,8 +2848,13 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     const float* pts;
     const int* n_src;
     if (c.scan) {
-      launch(ctx, "hs_project", k_hector_project, dim3(1), dim3(1024), 0, pc, (const float*)(h->d_ranges.p + (size_t)k * c.n_readings),
-             (const double2*)map->d_cossin.p, map->d_scan.p, d_n_live);
+      if (c.cloud)
+        launch(ctx, "hs_cloud_container", k_hector_cloud_container, dim3(1), dim3(1024), 0, pc,
+               (const float*)(h->d_xyz.p + (size_t)3 * k * c.n_readings), (const uint8_t*)(h->d_valid.p + (size_t)k * c.n_readings),
+               map->d_scan.p, d_n_live);
+      else
+        launch(ctx, "hs_project", k_hector_project, dim3(1), dim3(1024), 0, pc, (const float*)(h->d_ranges.p + (size_t)k * c.n_readings),
+               (const double2*)map->d_cossin.p, map->d_scan.p, d_n_live);
       pts = map->d_scan.p;
       n_src = d_n_live;
       sc.origo[0] = scan_origo[0]; sc.origo[1] = scan_origo[1];
@@ -2879,6 +2937,9 @@ void lslam_hector_destroy(lslam_hector* h) {
   h->d_rec.release();
   h->d_ranges.release();
   h->d_counts.release();
+  if (h->deskew) lslam_deskew_destroy(h->deskew);
+  h->d_xyz.release();
+  h->d_valid.release();
   delete h;
 }
 
@@ -2934,6 +2995,51 @@ int lslam_hector_process_many(lslam_hector* h, const lslam_hector_scan* scan, in
   c.capacity = n_readings;
   c.scan = scan;
   c.n_readings = n_readings;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.out = out;
+  return hs_run(h, c);
+}
+
+int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_readings,
+                                       const float* ranges, int ranges_stride, const lslam_deskew_params* params,
+                                       const int32_t* imu_first, const double* imu_time, const double* imu_rot_x,
+                                       const double* imu_rot_y, const double* imu_rot_z, const float* pose_hints,
+                                       const uint8_t* map_without_matching, lslam_hector_record* out) {
+  if (!h || n_scans < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_scans == 0) return LSLAM_OK;
+  if (!scan || !params || !imu_first || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  int rc = hs_check(h, "lslam_hector_process_many_deskewed", n_readings);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  if (!h->deskew) {
+    rc = lslam_deskew_create(ctx, &h->deskew);
+    if (rc) return rc;
+  }
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_readings, 1) + 4));
+  const size_t total = (size_t)n_scans * (size_t)n_readings;
+  LSLAM_HIP(ctx, h->d_ranges.reserve(std::max(total, (size_t)1)));
+  LSLAM_HIP(ctx, h->d_xyz.reserve(std::max(3 * total, (size_t)1)));
+  LSLAM_HIP(ctx, h->d_valid.reserve(std::max(total, (size_t)1)));
+  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, std::max(total, (size_t)1));
+  if (rc) return rc;
+  if (total > 0) {
+    for (int k = 0; k < n_scans; k++)
+      memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  // ONE de-skew launch for the whole call (it does not depend on the map), asynchronous on the same stream
+  rc = lslam_deskew_batch_dev(h->deskew, n_scans, n_readings, h->d_ranges.p, n_readings, params, imu_first, imu_time, imu_rot_x,
+                              imu_rot_y, imu_rot_z, h->d_xyz.p, h->d_valid.p);
+  if (rc) return rc;
+  HsCall c;
+  c.n_scans = n_scans;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.cloud = true;
   c.hints = pose_hints;
   c.no_match = map_without_matching;
   c.out = out;

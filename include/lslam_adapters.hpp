@@ -394,6 +394,20 @@ class HectorSlamProcessorGpu {
     check(lslam_hector_process_many_points(h_, nScans, pointsXY, nPoints, origosXY, poseHints,
                                            mapWithoutMatching ? flags_.data() : nullptr, records));
   }
+  // update() for nScans RAW LaserScans that lesson5 de-skews first (LidarUndistortionGpu::CorrectLaserScans' inputs): one
+  // batched de-skew launch for the call, then cloud -> DataContainer (rosPointCloudToDataContainer with `scan`'s filters and
+  // laser transform), match, mark and apply per scan -- still one host synchronisation.  lesson5's cloud has z ~ 1: the z
+  // window of `scan` must contain 1 or every container is empty.
+  void updateManyDeskewed(const lslam_hector_scan& scan, int nScans, int nReadings, const float* ranges, int rangesStride,
+                          const lslam_deskew_params* params, const int32_t* imuFirst, const double* imuTime,
+                          const double* imuRotX, const double* imuRotY, const double* imuRotZ, const float* poseHints,
+                          const bool* mapWithoutMatching, lslam_hector_record* records) {
+    flags_.assign((size_t)(nScans > 0 ? nScans : 0), 0);
+    for (int k = 0; k < nScans && mapWithoutMatching; ++k) flags_[(size_t)k] = mapWithoutMatching[k] ? 1 : 0;
+    check(lslam_hector_process_many_deskewed(h_, &scan, nScans, nReadings, ranges, rangesStride, params, imuFirst, imuTime,
+                                             imuRotX, imuRotY, imuRotZ, poseHints,
+                                             mapWithoutMatching ? flags_.data() : nullptr, records));
+  }
   void reset() { check(lslam_hector_reset(h_)); }  // :111-117
   // getLastScanMatchPose / getLastScanMatchCovariance (:120-122)
   void getLastScanMatchPose(float out[3]) { check(lslam_hector_state(h_, out, nullptr, nullptr)); }
@@ -418,6 +432,46 @@ class HectorSlamProcessorGpu {
   float minDist_ = 0.4f, minAngle_ = 0.13f;
   std::vector<float> pts_;
   std::vector<uint8_t> flags_;
+};
+
+// LidarUndistortion::CorrectLaserScan (lesson5/src/lidar_undistortion.cc:339-447) for many scans per launch.  The caller
+// keeps what the node's callbacks and Prune* steps produce -- per scan the header, the odometry increment and the
+// integrated IMU samples -- and hands a stretch of scans over at once; every scan's cloud is bit for bit what
+// lslam_deskew_scan returns for it.
+class LidarUndistortionGpu {
+ public:
+  explicit LidarUndistortionGpu(lslam_context* ctx) : ctx_(ctx) { check(lslam_deskew_create(ctx, &h_)); }
+  ~LidarUndistortionGpu() { lslam_deskew_destroy(h_); }
+  LidarUndistortionGpu(const LidarUndistortionGpu&) = delete;
+  LidarUndistortionGpu& operator=(const LidarUndistortionGpu&) = delete;
+
+  // nScans scans of nReadings beams (row k at ranges + k * rangesStride), one geometry; scan k owns the IMU samples
+  // [imuFirst[k], imuFirst[k + 1]).  outXYZ: nScans x nReadings x 3 (corrected_pointcloud_'s x, y, z; zeros where the
+  // reference skips a beam), outValid: nScans x nReadings.
+  void CorrectLaserScans(int nScans, int nReadings, const float* ranges, int rangesStride, const lslam_deskew_params* params,
+                         const int32_t* imuFirst, const double* imuTime, const double* imuRotX, const double* imuRotY,
+                         const double* imuRotZ, float* outXYZ, uint8_t* outValid) {
+    check(lslam_deskew_batch(h_, nScans, nReadings, ranges, rangesStride, params, imuFirst, imuTime, imuRotX, imuRotY, imuRotZ,
+                             outXYZ, outValid));
+  }
+  // the same with ranges, outXYZ and outValid in HBM: asynchronous on lslam_stream(ctx), no host wait
+  void CorrectLaserScansDev(int nScans, int nReadings, const float* rangesDev, int rangesStride,
+                            const lslam_deskew_params* params, const int32_t* imuFirst, const double* imuTime,
+                            const double* imuRotX, const double* imuRotY, const double* imuRotZ, float* outXYZDev,
+                            uint8_t* outValidDev) {
+    check(lslam_deskew_batch_dev(h_, nScans, nReadings, rangesDev, rangesStride, params, imuFirst, imuTime, imuRotX, imuRotY,
+                                 imuRotZ, outXYZDev, outValidDev));
+  }
+  // {scans de-skewed, kernel launches, buffer growths, host waits}
+  void stats(int64_t out[4]) const { lslam_deskew_stats(h_, out); }
+  lslam_deskew* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_deskew* h_ = nullptr;
 };
 
 // gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's

@@ -669,6 +669,20 @@ typedef struct lslam_hector_scan {
   float laser_x, laser_y, laser_z, laser_yaw; /* laserTransform_: base_link -> laser */
 } lslam_hector_scan;
 int lslam_map_set_scan(lslam_map* map, const float* ranges, int n, const lslam_hector_scan* scan, int* n_points);
+/* A de-skewed cloud -> DataContainer ON THE DEVICE: rosPointCloudToDataContainer (hector_slam.cc:320-362) applied to what
+ * lslam_deskew_scan / lslam_deskew_batch return (xyz: n x 3 float32, valid: n), the counterpart of lslam_map_set_scan for
+ * lesson5's output.  Only beams with valid = 1 enter, in beam order; d2 = x*x + y*y in float32 and the filters of :336-345;
+ * the transform is tf's double row . v + origin (planar: yaw + translation) and INCLUDES the point's z:
+ * pointPosLaserFrameZ = (float)(bz - tz) is tested against the z window (:351-353); the point becomes ((float)bx, (float)by)
+ * * scaleToMap.  Of `scan` the filter fields (sqr_laser_*_dist, use_max_scan_range, laser_z_min / laser_z_max) and the
+ * laser transform are read; angle_min, angle_increment, range_min, range_max and range_cutoff are IGNORED (the de-skew
+ * has applied the scan's own range window).  The container is left resident like lslam_map_set_scan's:
+ * lslam_map_match_container / lslam_map_update_by_container work on it.
+ * A consequence of composing the two lessons literally: lesson5 transforms (x, y, 1.0), so its cloud's z is ~ 1 (exactly 1
+ * for a planar robot: no roll or pitch rate, no odometry z), and the Hector node's default z window (-1, 1) -- both ends
+ * exclusive -- DROPS EVERY such POINT.  A caller who wants points passes a window that contains 1 (e.g. laser_z_max = 2). */
+int lslam_map_set_cloud(lslam_map* map, const float* xyz, const uint8_t* valid, int n, const lslam_hector_scan* scan,
+                        int* n_points);
 /* copies up to `capacity` points of the resident container (+ its origo) to the host; returns the container size */
 int lslam_map_read_container(lslam_map* map, float* out_xy, int capacity, float origo_xy[2]);
 int lslam_map_match_container(lslam_map* map, const float begin_world[3], float out_pose[3], float out_cov[9]);
@@ -745,6 +759,18 @@ int lslam_hector_process_many(lslam_hector* h, const lslam_hector_scan* scan, in
 int lslam_hector_process_many_points(lslam_hector* h, int n_scans, const float* points_xy, const int32_t* n_points,
                                      const float* origos_xy, const float* pose_hints, const uint8_t* map_without_matching,
                                      lslam_hector_record* out);
+/* the same for RAW scans that lesson5 de-skews first: ranges + params + IMU samples exactly as lslam_deskew_batch takes them
+ * (one geometry per call) go through ONE batched de-skew launch for the whole call, then every scan's cloud goes through
+ * rosPointCloudToDataContainer on the device (lslam_map_set_cloud's kernel; `scan` as there, origo as in the ranges form),
+ * match, mark and apply.  Nothing comes back before the end of the call: still one host synchronisation.  Afterwards the
+ * map's resident and cached containers are the last scan's.  Mind the z window (lslam_map_set_cloud).  The same
+ * LSLAM_ERR_UNSUPPORTED cases as lslam_hector_process_many; what lslam_deskew_batch refuses is refused here. */
+struct lslam_deskew_params;
+int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_readings,
+                                       const float* ranges, int ranges_stride, const struct lslam_deskew_params* params,
+                                       const int32_t* imu_first, const double* imu_time, const double* imu_rot_x,
+                                       const double* imu_rot_y, const double* imu_rot_z, const float* pose_hints,
+                                       const uint8_t* map_without_matching, lslam_hector_record* out);
 /* getLastScanMatchPose / getLastScanMatchCovariance (:120-122) and lastMapUpdatePose; any pointer may be NULL.  Host only. */
 int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_match_cov[9], float last_update_pose[3]);
 /* out = {scans processed, map updates made, calls that processed scans, waits for the stream those calls made}.  The last is
@@ -773,6 +799,34 @@ typedef struct lslam_deskew_params {
 int lslam_deskew_scan(lslam_context* ctx, const float* ranges, int n, const lslam_deskew_params* params,
                       const double* imu_time, const double* imu_rot_x, const double* imu_rot_y, const double* imu_rot_z,
                       int n_imu, float* out_xyz, uint8_t* out_valid);
+/* BATCHED de-skew: n_scans scans of one geometry per launch, grid (tiles of 256 beams x scans).  Every scan's output is
+ * bit for bit what lslam_deskew_scan returns for that scan alone (both kernels run one __device__ body).  The handle owns
+ * every device and pinned buffer a call needs -- a call of a shape it has seen allocates nothing -- and the double cos / sin
+ * table of the beam angles (CreateAngleCache, :162-173), computed on the device once per (angle_min, angle_increment,
+ * n_readings) and kept until another geometry arrives (a table of more beams serves a shorter scan of the same angles).
+ * ranges: row k at ranges + k * ranges_stride.  params[n_scans]: angle_min, angle_increment, range_min and range_max must
+ * be equal across one call (LSLAM_ERR_INVALID_ARGUMENT otherwise).  imu_first[n_scans + 1]: scan k owns the integrated
+ * samples [imu_first[k], imu_first[k+1]) of imu_time / imu_rot_* -- the state PruneImuDeque leaves, as for
+ * lslam_deskew_scan; a scan with use_imu = 0 may own none, one with use_imu = 1 must own at least one.
+ * out_xyz: n_scans x n_readings x 3 float32, out_valid: n_scans x n_readings.  n_scans == 0 is LSLAM_OK and launches
+ * nothing.  At most 65535 scans per call.
+ * The _dev form takes ranges, out_xyz and out_valid in HBM (params, imu_first and the IMU arrays stay host arrays and have
+ * been copied when it returns), is ASYNCHRONOUS on lslam_stream() and makes no host wait: its small inputs go up through a
+ * ring of 4 pinned slots, and only a caller more than 4 unfinished calls ahead of the device waits for one (counted). */
+typedef struct lslam_deskew lslam_deskew;
+int lslam_deskew_create(lslam_context* ctx, lslam_deskew** out);
+void lslam_deskew_destroy(lslam_deskew* d);
+int lslam_deskew_batch(lslam_deskew* d, int n_scans, int n_readings, const float* ranges, int ranges_stride,
+                       const lslam_deskew_params* params, const int32_t* imu_first, const double* imu_time,
+                       const double* imu_rot_x, const double* imu_rot_y, const double* imu_rot_z, float* out_xyz,
+                       uint8_t* out_valid);
+int lslam_deskew_batch_dev(lslam_deskew* d, int n_scans, int n_readings, const float* ranges_dev, int ranges_stride,
+                           const lslam_deskew_params* params, const int32_t* imu_first, const double* imu_time,
+                           const double* imu_rot_x, const double* imu_rot_y, const double* imu_rot_z, float* out_xyz_dev,
+                           uint8_t* out_valid_dev);
+/* out = {scans de-skewed, kernel launches (the angle table's included), buffer growths (device or pinned), host waits}.  A
+ * second call of a shape already seen reports no new growth; the host form waits once per call, at its end. */
+int lslam_deskew_stats(const lslam_deskew* d, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
 /* lesson4 GMapping hit/visit count map (lesson4_gmapping_node: GMapping::ComputeMap /        */
