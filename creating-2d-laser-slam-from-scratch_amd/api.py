@@ -410,6 +410,13 @@ def lib() -> C.CDLL:
     L.lslam_hector_process_many_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.lslam_hector_state.argtypes = [vp, vp, vp, vp]
     L.lslam_hector_stats.argtypes = [vp, vp]
+    L.lslam_hector_fleet_create.argtypes = [vp, i32, C.POINTER(vp)]
+    L.lslam_hector_fleet_destroy.argtypes = [vp]
+    L.lslam_hector_fleet_destroy.restype = None
+    L.lslam_hector_fleet_size.argtypes = [vp]
+    L.lslam_hector_fleet_process_many.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp]
+    L.lslam_hector_fleet_process_many_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_fleet_stats.argtypes = [vp, vp]
     L.lslam_pool_create.argtypes = [i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_create_on.argtypes = [vp, i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_destroy.argtypes = [vp]
@@ -1450,6 +1457,8 @@ class HectorProcessor:
 
     def close(self):
         if getattr(self, "h", None):
+            for fleet in list(getattr(self, "_fleets", ())):  # a HectorFleet borrows its processors
+                fleet.close()
             self.L.lslam_hector_destroy(self.h)
             self.h = None
             if self in getattr(self.map, "_processors", ()):
@@ -1545,6 +1554,97 @@ class HectorProcessor:
         out = (C.c_int64 * 4)()
         self.ctx.check(self.L.lslam_hector_stats(self.h, out))
         return dict(zip(("scans", "map_updates", "calls", "host_syncs"), (int(v) for v in out)))
+
+
+class HectorFleet:
+    """R HectorProcessors, each on its own map, advanced one scan each per step with the launches of ONE processor's chain
+    (lslam_hector_fleet_*).  Borrows the processors: each keeps its state, thresholds, options and map, and stays usable on
+    its own between fleet calls.  Per-scan arrays are [n_steps, R, ...]; `active` [n_steps, R] marks the scans that exist (a
+    scan that does not changes nothing of its member and comes back as a zero record with n_points = -1)."""
+
+    def __init__(self, processors):
+        self.processors = list(processors)
+        if not self.processors:
+            raise LslamError(-1, "a fleet needs at least one processor")
+        self.ctx, self.L = self.processors[0].ctx, self.processors[0].L
+        arr = (C.c_void_p * len(self.processors))(*[p.h for p in self.processors])
+        h = C.c_void_p()
+        self.ctx.check(self.L.lslam_hector_fleet_create(arr, len(self.processors), C.byref(h)))
+        self.h = h
+        for p in self.processors:
+            p.__dict__.setdefault("_fleets", []).append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_hector_fleet_destroy(self.h)
+            self.h = None
+            for p in self.processors:
+                if self in getattr(p, "_fleets", ()):
+                    p._fleets.remove(self)
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self) -> int:
+        return int(self.L.lslam_hector_fleet_size(self.h))
+
+    def _per_scan(self, n_steps, pose_hints, map_without_matching, active):
+        n = n_steps * len(self.processors)
+        hints = None if pose_hints is None else np.ascontiguousarray(pose_hints, dtype=np.float32).reshape(n, 3)
+        flags, act = (None if a is None else
+                      np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.uint8), (n_steps, len(self.processors)))).reshape(n)
+                      for a in (map_without_matching, active))
+        return hints, flags, act
+
+    def process_many(self, ranges, scan: HectorScan, pose_hints=None, map_without_matching=None, active=None) -> np.ndarray:
+        """ranges: [n_steps, R, n_readings] float32 LaserScans of one geometry -> HECTOR_RECORD[n_steps, R]."""
+        R = len(self.processors)
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        r = r.reshape(-1, R, r.shape[-1])
+        n_steps = r.shape[0]
+        hints, flags, act = self._per_scan(n_steps, pose_hints, map_without_matching, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_fleet_process_many(
+            self.h, C.byref(scan), n_steps, r.shape[2], r.ctypes.data, r.shape[2], None if hints is None else hints.ctypes.data,
+            None if flags is None else flags.ctypes.data, None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_points(self, containers, pose_hints=None, map_without_matching=None, active=None, origos_xy=None,
+                            counts=None) -> np.ndarray:
+        """containers[step][member]: (n, 2) float32 arrays in the member's level-0 cell units (None or empty where the scan
+        is not active), or -- with `counts` [n_steps, R] -- one packed array in step-major order."""
+        R = len(self.processors)
+        if counts is None:
+            flat = [np.zeros((0, 2), np.float32) if p is None else np.asarray(p, dtype=np.float32).reshape(-1, 2)
+                    for row in containers for p in row]
+            assert len(flat) % R == 0, "every step needs one container per member"
+            counts = np.array([len(p) for p in flat], dtype=np.int32)
+            pts = np.concatenate(flat) if flat else np.zeros((0, 2), np.float32)
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+            pts = np.asarray(containers, dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        n_steps = len(counts) // R
+        n = n_steps * R
+        hints, flags, act = self._per_scan(n_steps, pose_hints, map_without_matching, active)
+        o = None if origos_xy is None else np.ascontiguousarray(np.broadcast_to(np.asarray(origos_xy, dtype=np.float32), (n_steps, R, 2)))
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_fleet_process_many_points(
+            self.h, n_steps, pts.ctypes.data, counts.ctypes.data, None if o is None else o.ctypes.data,
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 6)()
+        self.ctx.check(self.L.lslam_hector_fleet_stats(self.h, out))
+        return dict(zip(("steps", "scans", "map_updates", "calls", "host_syncs", "launches"), (int(v) for v in out)))
 
 
 class GMappingMap:

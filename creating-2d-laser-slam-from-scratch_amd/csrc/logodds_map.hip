@@ -664,9 +664,10 @@ __device__ __forceinline__ bool hector_cloud_point(const ProjectCfg& c, float x,
   return true;
 }
 
-__global__ void __launch_bounds__(1024)
-k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* __restrict__ cossin,
-                 float* __restrict__ out_xy, int* __restrict__ out_n) {
+// one LaserScan -> DataContainer, one block of 1024 (k_hector_project, and k_hf_project with a member's configuration)
+__device__ __forceinline__ void hector_project_body(const ProjectCfg& c, const float* __restrict__ ranges,
+                                                    const double2* __restrict__ cossin, float* __restrict__ out_xy,
+                                                    int* __restrict__ out_n) {
   hector_compact(c.n, out_xy, out_n, [&](int i, float& ox, float& oy) {
     const float r = ranges[i];
     if (!(r < c.cutoff && r >= c.range_min)) return false;  // laser_geometry::projectLaser_ (NaN fails both)
@@ -674,6 +675,12 @@ k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* 
     const float x = (float)((double)r * cs.x), y = (float)((double)r * cs.y);  // sensor_msgs/PointCloud: float32
     return hector_cloud_point(c, x, y, 0.0f, ox, oy);                          // (projectLaser's cloud has z = 0)
   });
+}
+
+__global__ void __launch_bounds__(1024)
+k_hector_project(ProjectCfg c, const float* __restrict__ ranges, const double2* __restrict__ cossin,
+                 float* __restrict__ out_xy, int* __restrict__ out_n) {
+  hector_project_body(c, ranges, cossin, out_xy, out_n);
 }
 
 // A de-skewed cloud (lslam_deskew_*: xyz + valid per beam) -> DataContainer: rosPointCloudToDataContainer applied to the
@@ -712,6 +719,15 @@ struct GnLevels {
   float scale[kGnMaxLevels], t_x[kGnMaxLevels], t_y[kGnMaxLevels];
   const float* logodds[kGnMaxLevels];
 };
+
+// A pointer that a kernel reads from a table in memory is a generic one to the compiler, which then addresses through it with
+// flat instructions and a 64-bit address in vector registers; a kernel argument it knows to point into device memory (global
+// instructions: scalar base + 32-bit offset).  This says so for the former and changes nothing for the latter.
+template <class T>
+__device__ __forceinline__ T* in_device_memory(T* p) {
+  typedef T __attribute__((address_space(1))) * Global;
+  return (T*)(Global)(uintptr_t)p;  // (by way of the integer: a cast there and straight back folds away)
+}
 
 __device__ __forceinline__ float gn_prob(const float* lo, int index) {  // getGridProbability (GridMapLogOdds.h:123-127)
   float odds = (float)exp((double)lo[index]);
@@ -984,7 +1000,7 @@ __device__ __forceinline__ void gn_match_fast_body(const GnLevels& lv, const flo
   int flip = 0;
   for (int L = lv.n_levels - 1; L >= 0; --L) {
     if (n == 0) continue;
-    const float* lo = lv.logodds[L];
+    const float* lo = in_device_memory(lv.logodds[L]);
     const int sx = lv.sx[L], sy = lv.sy[L];
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
@@ -1109,7 +1125,7 @@ __device__ __forceinline__ void gn_match_reg_body(const GnLevels& lv, const floa
   int flip = 0;
   for (int L = lv.n_levels - 1; L >= 0; --L) {
     if (n == 0) continue;
-    const float* __restrict__ lo = lv.logodds[L];
+    const float* __restrict__ lo = in_device_memory(lv.logodds[L]);
     const int sx = lv.sx[L], sy = lv.sy[L];
     const float sc = lv.scale[L];
     const float factor = L == 0 ? 1.0f : 1.0f / (float)(1 << L);
@@ -1356,10 +1372,11 @@ __device__ __forceinline__ int hs_begin(const HsScan& sc, const int* n_src, cons
   return n;
 }
 
+// one streamed scan in either form of the matcher: k_hs_match_* take its arguments from the launch, k_hf_match_* from their
+// member's entries of the fleet's tables
 template <int NT, int PMAX>
-__global__ void __launch_bounds__(NT)
-k_hs_match_reg(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
-               HsState* st, lslam_hector_record* __restrict__ rec) {
+__device__ __forceinline__ void hs_scan_reg(const GnLevels& lv, const HsScan& sc, const float* __restrict__ pts, const int* n_src,
+                                            float* __restrict__ cache_dst, HsState* st, lslam_hector_record* __restrict__ rec) {
   float b[3], pose[3], H[9];
   const int n = hs_begin(sc, n_src, st, b);
   if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
@@ -1368,14 +1385,28 @@ k_hs_match_reg(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int*
 }
 
 template <int NT>
-__global__ void __launch_bounds__(NT)
-k_hs_match_fast(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
-                int pts_in_lds, HsState* st, lslam_hector_record* __restrict__ rec) {
+__device__ __forceinline__ void hs_scan_fast(const GnLevels& lv, const HsScan& sc, const float* __restrict__ pts, const int* n_src,
+                                             float* __restrict__ cache_dst, int pts_in_lds, HsState* st,
+                                             lslam_hector_record* __restrict__ rec) {
   float b[3], pose[3], H[9];
   const int n = hs_begin(sc, n_src, st, b);
   if (sc.no_match) { pose[0] = b[0]; pose[1] = b[1]; pose[2] = b[2]; }
   else gn_match_fast_body<NT>(lv, pts, cache_dst, n, pts_in_lds, b[0], b[1], b[2], pose, H);
   if (threadIdx.x == 0) hs_finish(lv, sc, st, rec, pose, H, n);
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_hs_match_reg(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
+               HsState* st, lslam_hector_record* __restrict__ rec) {
+  hs_scan_reg<NT, PMAX>(lv, sc, pts, n_src, cache_dst, st, rec);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_hs_match_fast(GnLevels lv, HsScan sc, const float* __restrict__ pts, const int* n_src, float* __restrict__ cache_dst,
+                int pts_in_lds, HsState* st, lslam_hector_record* __restrict__ rec) {
+  hs_scan_fast<NT>(lv, sc, pts, n_src, cache_dst, pts_in_lds, st, rec);
 }
 
 struct HsLevels {  // what does not change from scan to scan
@@ -1403,26 +1434,123 @@ __device__ __forceinline__ LevelGeom hs_level_geom(const HsLevels& lv, const HsS
 }
 
 // level 0 takes the live container, level i > 0 what the last matchData cached (MapRepMultiMap.h:174-191)
-__global__ void __launch_bounds__(256)
-k_hs_mark(HsLevels lv, const HsState* __restrict__ st, const float* __restrict__ pts_live, const float* __restrict__ pts_cached) {
+__device__ __forceinline__ void hs_mark_block(const HsLevels& lv, const HsState* __restrict__ st, const float* __restrict__ pts_live,
+                                              const float* __restrict__ pts_cached, int L) {
   if (!st->updated) return;
-  const int L = (int)blockIdx.y;
   const int n = L == 0 ? st->n_live : st->n_cached;
   const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   if (wave >= n) return;
-  logodds_mark_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63, lv.free_key[L],
-                    lv.occ_key[L], nullptr);
+  logodds_mark_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63,
+                    in_device_memory(lv.free_key[L]), in_device_memory(lv.occ_key[L]), nullptr);
+}
+
+__device__ __forceinline__ void hs_apply_block(const HsLevels& lv, const HsState* __restrict__ st, const float* __restrict__ pts_live,
+                                               const float* __restrict__ pts_cached, int L) {
+  if (!st->updated) return;
+  const int n = L == 0 ? st->n_live : st->n_cached;
+  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (wave >= n) return;
+  logodds_apply_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63,
+                     in_device_memory(lv.free_key[L]), in_device_memory(lv.occ_key[L]), in_device_memory(lv.logodds[L]));
+}
+
+__global__ void __launch_bounds__(256)
+k_hs_mark(HsLevels lv, const HsState* __restrict__ st, const float* __restrict__ pts_live, const float* __restrict__ pts_cached) {
+  hs_mark_block(lv, st, pts_live, pts_cached, (int)blockIdx.y);
 }
 
 __global__ void __launch_bounds__(256)
 k_hs_apply(HsLevels lv, const HsState* __restrict__ st, const float* __restrict__ pts_live, const float* __restrict__ pts_cached) {
-  if (!st->updated) return;
+  hs_apply_block(lv, st, pts_live, pts_cached, (int)blockIdx.y);
+}
+
+// ------------------------------------------------------------------------------------------
+// HECTOR FLEET (lslam_hector_fleet_*): R streamed processors, each on its own map, advance one scan each per STEP, and a step
+// is the chain of ONE processor -- [k_hf_project] -> k_hf_match_* -> k_hf_mark -> k_hf_apply -- whatever R is.  The members
+// are independent SLAM sessions, so nothing orders one against another inside a launch; within a member, stream order is
+// the only ordering, exactly as in the single processor's chain.  Every kernel finds its member in the grid (one matcher
+// or projection block per member: blockIdx.x; mark / apply: blockIdx.z) and reads two tables by that index:
+//   HfMember[R]          what does not change during a call: the pyramid as the matcher and as the update take it, the
+//                        projection's configuration, the member's state block and its cached and resident containers
+//   HfScan[step][R]      what the host knows of one (step, member): the HsScan the single kernels take as an argument, whether
+//                        the member takes part in the step, where its live container, its count and its record are
+// The index is uniform over a block, so the tables' words arrive through the scalar cache like kernel arguments do.  The
+// arithmetic is hs_scan_* / hs_mark_block / hs_apply_block / hector_project_body: a member's bits are those of its own
+// lslam_hector_* call.  A member that sits a step out returns before hs_begin's barrier and before any state is read: its
+// state block still holds the `updated` of its last scan.  Members may differ in size and depth: the mark / apply grid
+// covers the deepest pyramid and the longest container, and a block beyond its member's levels returns at once.
+// ------------------------------------------------------------------------------------------
+struct HfMember {
+  GnLevels gn;
+  HsLevels ul;
+  ProjectCfg pc;
+  HsState* st;
+  float* cached;    // the map's MapRepMultiMap::dataContainers buffer
+  float* resident;  // the map's lslam_map_set_scan container: the live container of the ranges form
+};
+struct HfScan {
+  HsScan sc;
+  int active;
+  const float* pts;     // live container: HfMember::resident, or this scan's points of the call
+  const int* n_src;     // its count: &st->n_live, or the call's
+  const float* ranges;  // ranges form: this scan's readings
+  lslam_hector_record* rec;
+};
+
+// Entry i of a table the host wrote before the launch and no kernel writes: read through the constant address space, so that
+// -- i being uniform over the block -- its words come through the scalar cache into scalar registers wherever the kernel
+// reads them, also behind its own stores (a plain global load behind a store is a vector load: k_hf_match_fast<256> then
+// needs 66 VGPRs where k_hs_match_fast<256> has 62, and drops from 8 waves per SIMD to 7).
+template <class T>
+__device__ __forceinline__ const T& hf_entry(const T* table, unsigned i) {
+  typedef const T __attribute__((address_space(4))) * ConstPtr;
+  return *(const T*)(ConstPtr)(uintptr_t)(table + i);  // (by way of the integer, as in_device_memory)
+}
+
+__global__ void __launch_bounds__(1024)
+k_hf_project(const HfMember* __restrict__ mem, const HfScan* __restrict__ step, const double2* __restrict__ cossin) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  hector_project_body(m.pc, in_device_memory(d.ranges), cossin, in_device_memory(m.resident), &in_device_memory(m.st)->n_live);
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_hf_match_reg(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  hs_scan_reg<NT, PMAX>(m.gn, d.sc, in_device_memory(d.pts), in_device_memory(d.n_src), in_device_memory(m.cached), in_device_memory(m.st), in_device_memory(d.rec));
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_hf_match_fast(const HfMember* __restrict__ mem, const HfScan* __restrict__ step, int pts_in_lds) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  hs_scan_fast<NT>(m.gn, d.sc, in_device_memory(d.pts), in_device_memory(d.n_src), in_device_memory(m.cached), pts_in_lds, in_device_memory(m.st), in_device_memory(d.rec));
+}
+
+__global__ void __launch_bounds__(256)
+k_hf_mark(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
+  const HfScan& d = hf_entry(step, blockIdx.z);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.z);
   const int L = (int)blockIdx.y;
-  const int n = L == 0 ? st->n_live : st->n_cached;
-  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  if (wave >= n) return;
-  logodds_apply_wave(hs_level_geom(lv, st, L), L == 0 ? pts_live : pts_cached, n, wave, threadIdx.x & 63, lv.free_key[L],
-                     lv.occ_key[L], lv.logodds[L]);
+  if (L >= m.ul.n_levels) return;
+  hs_mark_block(m.ul, in_device_memory(m.st), in_device_memory(d.pts), in_device_memory(m.cached), L);
+}
+
+__global__ void __launch_bounds__(256)
+k_hf_apply(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
+  const HfScan& d = hf_entry(step, blockIdx.z);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.z);
+  const int L = (int)blockIdx.y;
+  if (L >= m.ul.n_levels) return;
+  hs_apply_block(m.ul, in_device_memory(m.st), in_device_memory(d.pts), in_device_memory(m.cached), L);
 }
 
 float prob_to_logodds(float prob) {  // H/map/GridMapLogOdds.h:151-155 (log() is the double overload)
@@ -2769,6 +2897,47 @@ struct HsCall {
   lslam_hector_record* out = nullptr;
 };
 
+// the cached container must survive a growth of its buffer (levels above 0 of a scan taken without matching read it);
+// *cache_cap: the points either container of a scan of this call may hold
+int hs_reserve_cached(lslam_map* map, int capacity, int* cache_cap) {
+  lslam_context* ctx = map->ctx;
+  *cache_cap = std::max(std::max(capacity, map->n_cached), 1);
+  const float* old = map->d_cached.p;
+  LSLAM_HIP(ctx, map->d_cached.reserve((size_t)2 * *cache_cap));
+  if (old && old != map->d_cached.p && map->n_cached > 0)
+    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_cached.p, old, (size_t)2 * map->n_cached * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  return LSLAM_OK;
+}
+
+HsLevels hs_levels_of(const lslam_map* map) {  // the pyramid as the streamed update's kernels take it
+  HsLevels ul;
+  ul.n_levels = (int)map->levels.size();
+  ul.lo_free = map->lo_free;
+  ul.lo_occ = map->lo_occ;
+  for (int i = 0; i < ul.n_levels; i++) {
+    const Level& L = map->levels[i];
+    ul.sx[i] = L.sx; ul.sy[i] = L.sy;
+    ul.free_key[i] = L.d_free; ul.occ_key[i] = L.d_occ; ul.logodds[i] = L.d_logodds;
+  }
+  return ul;
+}
+
+// what the host knows of one scan, but for its origo and its epochs
+HsScan hs_scan_of(const lslam_hector* h, const float* hint, bool no_match, int capacity) {
+  HsScan sc{};
+  sc.chain = hint ? 0 : 1;
+  sc.no_match = no_match ? 1 : 0;
+  if (hint) {
+    for (int q = 0; q < 3; q++) sc.hint[q] = hint[q];
+    sc.hint_c = cosf(sc.hint[2]);  // host libm, exactly what the reference's Eigen::Rotation2Df evaluates
+    sc.hint_s = sinf(sc.hint[2]);
+    sc.host_trig = sc.no_match;
+  }
+  sc.min_dist = h->min_dist; sc.min_angle = h->min_angle; sc.fabs_gate = h->fabs_gate;
+  sc.capacity = capacity;
+  return sc;
+}
+
 int hs_run(lslam_hector* h, const HsCall& c) {
   lslam_map* map = h->map;
   lslam_context* ctx = map->ctx;
@@ -2777,13 +2946,10 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     int rc = flush_pending(map);  // the matcher reads the float planes; the streamed update is not deferred
     if (rc) return rc;
   }
-  // the cached container must survive a growth of its buffer (levels above 0 of a scan taken without matching read it)
-  const int cache_cap = std::max(std::max(c.capacity, map->n_cached), 1);
+  int cache_cap = 1;
   {
-    const float* old = map->d_cached.p;
-    LSLAM_HIP(ctx, map->d_cached.reserve((size_t)2 * cache_cap));
-    if (old && old != map->d_cached.p && map->n_cached > 0)
-      LSLAM_HIP(ctx, hipMemcpyAsync(map->d_cached.p, old, (size_t)2 * map->n_cached * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    int rc = hs_reserve_cached(map, c.capacity, &cache_cap);
+    if (rc) return rc;
   }
   LSLAM_HIP(ctx, h->d_rec.reserve((size_t)c.n_scans));
   {
@@ -2799,15 +2965,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   memcpy(h->h_io, &h->mirror, kHsPersistWords * 4);
   LSLAM_HIP(ctx, hipMemcpyAsync(h->d_state, h->h_io, kHsPersistWords * 4, hipMemcpyHostToDevice, ctx->stream));
   const GnLevels lv = gn_levels_of(map);
-  HsLevels ul;
-  ul.n_levels = n_levels;
-  ul.lo_free = map->lo_free;
-  ul.lo_occ = map->lo_occ;
-  for (int i = 0; i < n_levels; i++) {
-    const Level& L = map->levels[i];
-    ul.sx[i] = L.sx; ul.sy[i] = L.sy;
-    ul.free_key[i] = L.d_free; ul.occ_key[i] = L.d_occ; ul.logodds[i] = L.d_logodds;
-  }
+  const HsLevels ul = hs_levels_of(map);
   int* const d_n_live = &h->d_state->n_live;
   ProjectCfg pc{};
   float scan_origo[2] = {0.f, 0.f};
@@ -2825,17 +2983,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   const GnForm form = gn_form_of(map, c.capacity);
   const dim3 ugrid((unsigned)((cache_cap + 3) / 4), (unsigned)n_levels), ublock(256);
   for (int k = 0; k < c.n_scans; k++) {
-    HsScan sc{};
-    sc.chain = c.hints ? 0 : 1;
-    sc.no_match = c.no_match && c.no_match[k] ? 1 : 0;
-    if (c.hints) {
-      for (int q = 0; q < 3; q++) sc.hint[q] = c.hints[3 * k + q];
-      sc.hint_c = cosf(sc.hint[2]);  // host libm, exactly what the reference's Eigen::Rotation2Df evaluates
-      sc.hint_s = sinf(sc.hint[2]);
-      sc.host_trig = sc.no_match;
-    }
-    sc.min_dist = h->min_dist; sc.min_angle = h->min_angle; sc.fabs_gate = h->fabs_gate;
-    sc.capacity = c.capacity;
+    HsScan sc = hs_scan_of(h, c.hints ? c.hints + 3 * k : nullptr, c.no_match && c.no_match[k], c.capacity);
     // an epoch per scan and level whether or not the device updates (an unused epoch is harmless)
     for (int li = 0; li < n_levels; li++) {
       Level& L = map->levels[li];
@@ -3102,6 +3250,388 @@ int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_mat
 int lslam_hector_stats(const lslam_hector* h, int64_t out[4]) {
   if (!h || !out) return LSLAM_ERR_INVALID_ARGUMENT;
   out[0] = h->n_scans; out[1] = h->n_updates; out[2] = h->n_calls; out[3] = h->n_syncs;
+  return LSLAM_OK;
+}
+
+}  // extern "C"
+
+
+// ------------------------------------------------------------------------------------------
+// lslam_hector_fleet_*: many streamed processors stepped in lockstep launches (device side: k_hf_* above)
+// ------------------------------------------------------------------------------------------
+struct lslam_hector_fleet {
+  lslam_context* ctx = nullptr;
+  std::vector<lslam_hector*> members;
+  // The device tables, and the members' state blocks of a call side by side: one copy up and one down per call instead of
+  // one per member.  What a member IS stays in its own mirror and map: the blocks are filled from them at the start of a
+  // call and handed back at its end, as the member's own calls do with its own block.
+  HfMember* d_mem = nullptr;
+  HsState* d_state = nullptr;
+  DevBuf<HfScan> d_step;
+  DevBuf<lslam_hector_record> d_rec;
+  DevBuf<float> d_in;     // the call's ranges, or its points
+  DevBuf<int> d_counts;
+  // pinned staging, the fleet's own
+  HfMember* h_mem = nullptr;
+  HsState* h_state = nullptr;  // [2][R]: up, down
+  HfScan* h_step = nullptr;
+  size_t h_step_cap = 0;
+  lslam_hector_record* h_rec = nullptr;
+  size_t h_rec_cap = 0;
+  float* h_in = nullptr;  // ranges, or points and then counts
+  size_t h_in_cap = 0;
+  int64_t n_steps = 0, n_scans = 0, n_updates = 0, n_calls = 0, n_syncs = 0, n_launches = 0;
+};
+
+namespace {
+
+constexpr int kHfMaxMembers = 4096;
+
+struct HfCall {
+  int n_steps = 0, capacity = 0;
+  const lslam_hector_scan* scan = nullptr;  // ranges form
+  int n_readings = 0;
+  const int32_t* n_points = nullptr;        // container form: host counts (offsets into d_in) and
+  const float* origos = nullptr;            //   origos (may be null)
+  const float* hints = nullptr;
+  const uint8_t* no_match = nullptr;
+  const uint8_t* active = nullptr;
+  lslam_hector_record* out = nullptr;
+};
+
+struct HfWrap { int step, member, level; };  // a key plane whose epochs run out in front of this step
+
+// what a call refuses before anything is enqueued
+int hf_check(lslam_hector_fleet* f, const char* who, int capacity) {
+  for (lslam_hector* h : f->members) {
+    int rc = hs_check(h, who, capacity);
+    if (rc) return rc;
+  }
+  return LSLAM_OK;
+}
+
+int hf_run(lslam_hector_fleet* f, const HfCall& c) {
+  lslam_context* ctx = f->ctx;
+  const int R = (int)f->members.size();
+  const size_t total = (size_t)c.n_steps * (size_t)R;
+  const bool ranges_form = c.scan != nullptr;
+  std::vector<int> n_active((size_t)R, 0);  // scans each member takes in this call
+  for (size_t i = 0; i < total; i++) n_active[i % (size_t)R] += !c.active || c.active[i];
+  int ucap = 1, max_levels = 1;
+  for (int m = 0; m < R; m++) {
+    lslam_map* map = f->members[m]->map;
+    // (growing a resident container drops what it holds: only for a member whose scans are about to replace it)
+    if (ranges_form && n_active[m]) LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(c.n_readings, 1) + 4));
+    int rc = flush_pending(map);  // the matcher reads the float planes; the streamed update is not deferred
+    if (rc) return rc;
+    int cache_cap = 1;
+    rc = hs_reserve_cached(map, c.capacity, &cache_cap);
+    if (rc) return rc;
+    ucap = std::max(ucap, cache_cap);
+    max_levels = std::max(max_levels, (int)map->levels.size());
+  }
+  LSLAM_HIP(ctx, f->d_step.reserve(total));
+  LSLAM_HIP(ctx, f->d_rec.reserve(total));
+  {
+    int rc = hs_pinned_reserve(ctx, &f->h_step, &f->h_step_cap, total);
+    if (!rc) rc = hs_pinned_reserve(ctx, &f->h_rec, &f->h_rec_cap, total);
+    if (rc) return rc;
+  }
+  // ---- the member table and the state blocks up: every processor's vectors from its mirror, the cached container's count
+  // and origo from its map (a call of the member's own, or a host-driven matchData, may have replaced it since)
+  for (int m = 0; m < R; m++) {
+    lslam_hector* h = f->members[m];
+    lslam_map* map = h->map;
+    h->mirror.n_cached = map->n_cached;
+    h->mirror.cached_origo[0] = map->cached_origo[0];
+    h->mirror.cached_origo[1] = map->cached_origo[1];
+    h->mirror.updated = 0;
+    memcpy(&f->h_state[m], &h->mirror, sizeof(HsState));
+    HfMember& hm = f->h_mem[m];
+    hm.gn = gn_levels_of(map);
+    hm.ul = hs_levels_of(map);
+    hm.pc = ranges_form ? project_cfg(map, c.n_readings, c.scan) : ProjectCfg{};
+    hm.st = f->d_state + m;
+    hm.cached = map->d_cached.p;
+    hm.resident = map->d_scan.p;
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_mem, f->h_mem, (size_t)R * sizeof(HfMember), hipMemcpyHostToDevice, ctx->stream));
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_state, f->h_state, (size_t)R * sizeof(HsState), hipMemcpyHostToDevice, ctx->stream));
+  // ---- the descriptors of the whole call.  An epoch per ACTIVE scan and level whether or not the device updates (an unused
+  // epoch is harmless); a plane whose epochs run out is cleared in front of the step that starts them again.
+  std::vector<size_t> first;
+  if (!ranges_form) {
+    first.assign(total + 1, 0);
+    for (size_t i = 0; i < total; i++) first[i + 1] = first[i] + (size_t)c.n_points[i];
+  }
+  std::vector<uint32_t> epoch((size_t)R * kGnMaxLevels, 0);
+  for (int m = 0; m < R; m++)
+    for (size_t li = 0; li < f->members[m]->map->levels.size(); li++) epoch[(size_t)m * kGnMaxLevels + li] = f->members[m]->map->levels[li].epoch;
+  std::vector<HfWrap> wraps;
+  for (int k = 0; k < c.n_steps; k++) {
+    for (int m = 0; m < R; m++) {
+      const size_t i = (size_t)k * R + m;
+      lslam_hector* h = f->members[m];
+      lslam_map* map = h->map;
+      HfScan& d = f->h_step[i];
+      d = HfScan{};
+      d.active = !c.active || c.active[i] ? 1 : 0;
+      if (!d.active) continue;
+      d.sc = hs_scan_of(h, c.hints ? c.hints + 3 * i : nullptr, c.no_match && c.no_match[i], c.capacity);
+      for (int li = 0; li < (int)map->levels.size(); li++) {
+        uint32_t& e = epoch[(size_t)m * kGnMaxLevels + li];
+        if (e >= kMaxEpoch) {
+          wraps.push_back({k, m, li});
+          e = 0;
+        }
+        d.sc.epoch[li] = ++e;
+      }
+      if (ranges_form) {
+        // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:331)
+        d.sc.origo[0] = (float)(double)c.scan->laser_x * f->h_mem[m].pc.scale_to_map;
+        d.sc.origo[1] = (float)(double)c.scan->laser_y * f->h_mem[m].pc.scale_to_map;
+        d.pts = map->d_scan.p;
+        d.n_src = &(f->d_state + m)->n_live;
+        d.ranges = f->d_in.p + i * (size_t)c.n_readings;
+      } else {
+        d.sc.origo[0] = c.origos ? c.origos[2 * i] : 0.f;
+        d.sc.origo[1] = c.origos ? c.origos[2 * i + 1] : 0.f;
+        d.pts = f->d_in.p + 2 * first[i];
+        d.n_src = f->d_counts.p + i;
+      }
+      d.rec = f->d_rec.p + i;
+    }
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_step.p, f->h_step, total * sizeof(HfScan), hipMemcpyHostToDevice, ctx->stream));
+  // the matcher's form from the call's CAPACITY and the members' common LSLAM_GN_THREADS, as the single processor chooses it
+  const GnForm form = gn_form_of(f->members[0]->map, c.capacity);
+  const double2* cossin = f->members[0]->map->d_cossin.p;  // (the table follows from the scan geometry alone)
+  const dim3 ugrid((unsigned)((ucap + 3) / 4), (unsigned)max_levels, (unsigned)R), ublock(256);
+  size_t w = 0;
+  for (int k = 0; k < c.n_steps; k++) {
+    for (; w < wraps.size() && wraps[w].step == k; w++) {
+      lslam_map* map = f->members[wraps[w].member]->map;
+      int rc = clear_marks(map, map->levels[wraps[w].level]);  // stream-ordered, behind step k-1's apply; nothing is pending
+      if (rc) return rc;
+    }
+    const HfMember* mem = f->d_mem;
+    const HfScan* step = f->d_step.p + (size_t)k * R;
+    if (ranges_form) {
+      launch(ctx, "hf_project", k_hf_project, dim3(R), dim3(1024), 0, mem, step, cossin);
+      f->n_launches++;
+    }
+#define LSLAM_HF_REG(NT, PMAX) launch(ctx, "hf_match", k_hf_match_reg<NT, PMAX>, dim3(R), dim3(NT), form.lds, mem, step)
+#define LSLAM_HF_FAST(NT) launch(ctx, "hf_match", k_hf_match_fast<NT>, dim3(R), dim3(NT), form.lds, mem, step, form.in_lds)
+    LSLAM_GN_DISPATCH(form, LSLAM_HF_REG, LSLAM_HF_FAST);
+#undef LSLAM_HF_REG
+#undef LSLAM_HF_FAST
+    launch(ctx, "hf_mark", k_hf_mark, ugrid, ublock, 0, mem, step);
+    launch(ctx, "hf_apply", k_hf_apply, ugrid, ublock, 0, mem, step);
+    f->n_launches += 3;
+  }
+  for (int m = 0; m < R; m++)
+    for (size_t li = 0; li < f->members[m]->map->levels.size(); li++) f->members[m]->map->levels[li].epoch = epoch[(size_t)m * kGnMaxLevels + li];
+  LSLAM_HIP(ctx, hipGetLastError());
+  // ---- end of the call: the records and the state blocks down, ONE wait
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->h_rec, f->d_rec.p, total * sizeof(lslam_hector_record), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->h_state + R, f->d_state, (size_t)R * sizeof(HsState), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  f->n_syncs++;
+  f->n_calls++;
+  f->n_steps += c.n_steps;
+  for (size_t i = 0; i < total; i++) {
+    lslam_hector_record& r = f->h_rec[i];
+    if (!f->h_step[i].active) {  // a scan that was not taken: all zero but the count
+      memset(&r, 0, sizeof r);
+      r.n_points = -1;
+      continue;
+    }
+    lslam_hector* h = f->members[i % (size_t)R];
+    h->n_scans++;
+    h->n_updates += r.updated != 0;
+    f->n_scans++;
+    f->n_updates += r.updated != 0;
+  }
+  if (c.out) memcpy(c.out, f->h_rec, total * sizeof(lslam_hector_record));
+  // what each member and the host side of its map must know so that lslam_hector_* and lslam_map_* go on working on them
+  for (int m = 0; m < R; m++) {
+    if (!n_active[m]) continue;  // (its block came back as it went up)
+    lslam_hector* h = f->members[m];
+    lslam_map* map = h->map;
+    memcpy(&h->mirror, &f->h_state[R + m], kHsPersistWords * 4);
+    if (map->levels.size() > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
+      map->n_cached = h->mirror.n_cached;
+      map->cached_origo[0] = h->mirror.cached_origo[0];
+      map->cached_origo[1] = h->mirror.cached_origo[1];
+    }
+    map->gn_host_n = -1;  // d_cached was rewritten on the device
+    if (ranges_form) {    // the resident container of lslam_map_set_scan is the member's last scan's
+      map->n_scan = h->mirror.n_live;
+      map->scan_origo[0] = (float)(double)c.scan->laser_x * f->h_mem[m].pc.scale_to_map;
+      map->scan_origo[1] = (float)(double)c.scan->laser_y * f->h_mem[m].pc.scale_to_map;
+    }
+  }
+  return LSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lslam_hector_fleet_create(lslam_hector* const* members, int n_members, lslam_hector_fleet** out) {
+  if (!members || !out || n_members < 1) return LSLAM_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  for (int m = 0; m < n_members; m++)
+    if (!members[m]) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = members[0]->map->ctx;
+  for (int m = 0; m < n_members; m++) {
+    if (members[m]->map->ctx != ctx)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_create: member %d belongs to another context", m);
+    for (int q = 0; q < m; q++) {
+      if (members[q] == members[m])
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_create: members %d and %d are the same processor", q, m);
+      if (members[q]->map == members[m]->map)
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_create: members %d and %d share one map", q, m);
+    }
+  }
+  if (n_members > kHfMaxMembers)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_create: at most %d members (got %d)", kHfMaxMembers, n_members);
+  for (int m = 0; m < n_members; m++) {
+    const lslam_map* map = members[m]->map;
+    if (gn_form_of(map, 0).nt != gn_form_of(members[0]->map, 0).nt)
+      return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_create: member %d's map was created under another LSLAM_GN_THREADS "
+                       "than member 0's; one launch runs one form of the matcher", m);
+    if (map->ordered_sums)
+      return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_create: member %d's map is an LSLAM_MAP_OPT_ORDERED_SUMS map; the "
+                       "streamed processor runs the parallel-sum matcher", m);
+    if ((int)map->levels.size() > kGnMaxLevels)
+      return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_create: at most %d pyramid levels (member %d)", kGnMaxLevels, m);
+  }
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  lslam_hector_fleet* f = new lslam_hector_fleet();
+  f->ctx = ctx;
+  f->members.assign(members, members + n_members);
+  const size_t R = (size_t)n_members;
+  if (hipMalloc((void**)&f->d_mem, R * sizeof(HfMember)) != hipSuccess ||
+      hipMalloc((void**)&f->d_state, R * sizeof(HsState)) != hipSuccess ||
+      hipHostMalloc((void**)&f->h_mem, R * sizeof(HfMember), hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void**)&f->h_state, 2 * R * sizeof(HsState), hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    lslam_hector_fleet_destroy(f);
+    return ctx->fail(LSLAM_ERR_HIP, "cannot allocate the fleet's tables");
+  }
+  memset(f->h_mem, 0, R * sizeof(HfMember));
+  memset(f->h_state, 0, 2 * R * sizeof(HsState));
+  *out = f;
+  return LSLAM_OK;
+}
+
+void lslam_hector_fleet_destroy(lslam_hector_fleet* f) {
+  if (!f) return;
+  (void)hipSetDevice(f->ctx->device);
+  (void)hipStreamSynchronize(f->ctx->stream);
+  if (f->d_mem) (void)hipFree(f->d_mem);
+  if (f->d_state) (void)hipFree(f->d_state);
+  if (f->h_mem) (void)hipHostFree(f->h_mem);
+  if (f->h_state) (void)hipHostFree(f->h_state);
+  if (f->h_step) (void)hipHostFree(f->h_step);
+  if (f->h_rec) (void)hipHostFree(f->h_rec);
+  if (f->h_in) (void)hipHostFree(f->h_in);
+  f->d_step.release();
+  f->d_rec.release();
+  f->d_in.release();
+  f->d_counts.release();
+  delete f;
+}
+
+int lslam_hector_fleet_size(const lslam_hector_fleet* f) { return f ? (int)f->members.size() : LSLAM_ERR_INVALID_ARGUMENT; }
+
+int lslam_hector_fleet_process_many(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_readings,
+                                    const float* ranges, int ranges_stride, const float* pose_hints,
+                                    const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out) {
+  if (!f || n_steps < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  if (!scan || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  int rc = hf_check(f, "lslam_hector_fleet_process_many", n_readings);
+  if (rc) return rc;
+  const size_t rows = (size_t)n_steps * f->members.size();
+  const size_t total = rows * (size_t)n_readings;
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many: call too large");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  bool rebuilt = false;
+  rc = ensure_cossin(f->members[0]->map, n_readings, scan, &rebuilt);  // (waits for its upload when the scan geometry is new)
+  if (rc) return rc;
+  f->n_syncs += rebuilt;
+  LSLAM_HIP(ctx, f->d_in.reserve(std::max(total, (size_t)1)));
+  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, std::max(total, (size_t)1));
+  if (rc) return rc;
+  if (total > 0) {
+    for (size_t i = 0; i < rows; i++)
+      memcpy(f->h_in + i * n_readings, ranges + i * (size_t)ranges_stride, (size_t)n_readings * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.active = active;
+  c.out = out;
+  return hf_run(f, c);
+}
+
+int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, const float* points_xy, const int32_t* n_points,
+                                           const float* origos_xy, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out) {
+  if (!f || n_steps < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  if (!n_points) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  const size_t rows = (size_t)n_steps * f->members.size();
+  size_t total = 0;
+  int cap = 0;
+  for (size_t i = 0; i < rows; i++) {
+    if (n_points[i] < 0)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: scan %zu has a negative point count (%d)", i, n_points[i]);
+    if (active && !active[i] && n_points[i] != 0)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: scan %zu is not active but has %d points", i, n_points[i]);
+    total += (size_t)n_points[i];
+    cap = std::max(cap, n_points[i]);
+  }
+  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: points_xy is required");
+  int rc = hf_check(f, "lslam_hector_fleet_process_many_points", cap);
+  if (rc) return rc;
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_points: call too large");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t words = 2 * total + rows;
+  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, words);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, f->d_in.reserve(std::max((size_t)2 * total, (size_t)2)));
+  LSLAM_HIP(ctx, f->d_counts.reserve(rows));
+  if (total > 0) {
+    memcpy(f->h_in, points_xy, 2 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, 2 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  memcpy(f->h_in + 2 * total, n_points, rows * sizeof(int32_t));
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_counts.p, f->h_in + 2 * total, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = cap;
+  c.n_points = n_points;
+  c.origos = origos_xy;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.active = active;
+  c.out = out;
+  return hf_run(f, c);
+}
+
+int lslam_hector_fleet_stats(const lslam_hector_fleet* f, int64_t out[6]) {
+  if (!f || !out) return LSLAM_ERR_INVALID_ARGUMENT;
+  out[0] = f->n_steps; out[1] = f->n_scans; out[2] = f->n_updates; out[3] = f->n_calls; out[4] = f->n_syncs; out[5] = f->n_launches;
   return LSLAM_OK;
 }
 

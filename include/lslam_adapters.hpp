@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -432,6 +433,101 @@ class HectorSlamProcessorGpu {
   float minDist_ = 0.4f, minAngle_ = 0.13f;
   std::vector<float> pts_;
   std::vector<uint8_t> flags_;
+};
+
+// R HectorSlamProcessorGpu advanced together (lslam_hector_fleet_*): one robot's scan k+1 needs its scan k, but robots need
+// nothing of one another, so a STEP -- one scan of every member -- costs the launches of one processor's scan.  Either owns
+// its processors (all of one construction) or borrows the caller's (any mix of map sizes, resolutions and depths; they must
+// outlive the fleet).  Between calls every member is a HectorSlamProcessorGpu like any other.
+class HectorSlamFleetGpu {
+ public:
+  // nMembers x HectorSlamProcessor(mapResolution, mapSizeX, mapSizeY, startCoords, multi_res_size)
+  HectorSlamFleetGpu(lslam_context* ctx, int nMembers, float mapResolution, int mapSizeX, int mapSizeY, float startX, float startY,
+                     int multi_res_size)
+      : ctx_(ctx) {
+    for (int r = 0; r < nMembers; ++r) {
+      owned_.emplace_back(new HectorSlamProcessorGpu(ctx, mapResolution, mapSizeX, mapSizeY, startX, startY, multi_res_size));
+      members_.push_back(owned_.back().get());
+    }
+    create();
+  }
+  // the caller's processors, borrowed
+  HectorSlamFleetGpu(lslam_context* ctx, HectorSlamProcessorGpu* const* members, int nMembers)
+      : ctx_(ctx), members_(members, members + (nMembers > 0 ? nMembers : 0)) {
+    create();
+  }
+  ~HectorSlamFleetGpu() { lslam_hector_fleet_destroy(h_); }  // (before owned_: the fleet goes first)
+  HectorSlamFleetGpu(const HectorSlamFleetGpu&) = delete;
+  HectorSlamFleetGpu& operator=(const HectorSlamFleetGpu&) = delete;
+
+  int size() const { return (int)members_.size(); }
+  HectorSlamProcessorGpu& member(int r) { return *members_[(size_t)r]; }
+
+  // HectorSlamProcessor::update (:81) for one step: dataContainers[r] / poseHintsWorld[r] are member r's, in the reference's
+  // shapes (getSize() / getVecEntry(i) / getOrigo(); a pose indexable by [0..2]).  active: size() flags or nullptr = all; a
+  // member that is not active is not touched (its container is not read).
+  template <typename Container, typename Pose>
+  void update(const Container* dataContainers, const Pose* poseHintsWorld, bool map_without_matching = false,
+              const bool* active = nullptr, lslam_hector_record* records = nullptr) {
+    const int R = size();
+    pts_.clear();
+    counts_.assign((size_t)R, 0);
+    origos_.assign((size_t)2 * R, 0.f);
+    hints_.assign((size_t)3 * R, 0.f);
+    for (int r = 0; r < R; ++r) {
+      if (active && !active[r]) continue;
+      const Container& c = dataContainers[r];
+      const int n = c.getSize();
+      counts_[(size_t)r] = n;
+      for (int i = 0; i < n; ++i) {
+        pts_.push_back(c.getVecEntry(i)[0]);
+        pts_.push_back(c.getVecEntry(i)[1]);
+      }
+      origos_[(size_t)2 * r] = c.getOrigo()[0];
+      origos_[(size_t)2 * r + 1] = c.getOrigo()[1];
+      for (int q = 0; q < 3; ++q) hints_[(size_t)3 * r + q] = poseHintsWorld[r][q];
+    }
+    flags_.assign((size_t)R, map_without_matching ? 1 : 0);
+    active_.assign((size_t)R, 1);
+    for (int r = 0; r < R && active; ++r) active_[(size_t)r] = active[r] ? 1 : 0;
+    if (pts_.empty()) pts_.resize(2);
+    updateMany(1, pts_.data(), counts_.data(), origos_.data(), hints_.data(), flags_.data(), active ? active_.data() : nullptr,
+               records);
+  }
+  // nSteps steps of containers back to back, every per-scan array indexed step * size() + member as
+  // lslam_hector_fleet_process_many_points takes them; poseHints == nullptr: every member chains from its own last pose
+  void updateMany(int nSteps, const float* pointsXY, const int32_t* nPoints, const float* origosXY, const float* poseHints,
+                  const uint8_t* mapWithoutMatching, const uint8_t* active, lslam_hector_record* records) {
+    check(lslam_hector_fleet_process_many_points(h_, nSteps, pointsXY, nPoints, origosXY, poseHints, mapWithoutMatching, active,
+                                                 records));
+  }
+  // the same for LaserScans of one geometry: ranges row step * size() + member
+  void updateManyScans(const lslam_hector_scan& scan, int nSteps, int nReadings, const float* ranges, int rangesStride,
+                       const float* poseHints, const uint8_t* mapWithoutMatching, const uint8_t* active,
+                       lslam_hector_record* records) {
+    check(lslam_hector_fleet_process_many(h_, &scan, nSteps, nReadings, ranges, rangesStride, poseHints, mapWithoutMatching,
+                                          active, records));
+  }
+  // {steps, member-scans, map updates, calls, host waits, launches of the fleet's kernels}
+  void stats(int64_t out[6]) const { lslam_hector_fleet_stats(h_, out); }
+  lslam_hector_fleet* handle() { return h_; }
+
+ private:
+  void create() {
+    std::vector<lslam_hector*> hs;
+    for (HectorSlamProcessorGpu* p : members_) hs.push_back(p ? p->handle() : nullptr);
+    check(lslam_hector_fleet_create(hs.data(), (int)hs.size(), &h_));
+  }
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  std::vector<std::unique_ptr<HectorSlamProcessorGpu>> owned_;
+  std::vector<HectorSlamProcessorGpu*> members_;
+  lslam_hector_fleet* h_ = nullptr;
+  std::vector<float> pts_, origos_, hints_;
+  std::vector<int32_t> counts_;
+  std::vector<uint8_t> flags_, active_;
 };
 
 // LidarUndistortion::CorrectLaserScan (lesson5/src/lidar_undistortion.cc:339-447) for many scans per launch.  The caller

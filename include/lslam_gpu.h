@@ -781,6 +781,47 @@ int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_mat
 int lslam_hector_stats(const lslam_hector* h, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
+/* Hector fleet: many streamed processors, each on its own map, stepped in lockstep launches.  */
+/* ---------------------------------------------------------------------------------------- */
+/* Within one processor a scan's chain of launches is a true dependency; across processors it is not.  A fleet BORROWS
+ * R = n_members existing lslam_hector processors (destroy the fleet first) and advances every one of them by one scan per
+ * STEP with the launches of ONE chain: [projection], match, mark, apply -- 4 per step in the ranges form, 3 in the container
+ * form, whatever R is.  It keeps no SLAM state of its own: thresholds, the gate option, the three state vectors, the
+ * covariance and the map are the member's, read at the start of a call and handed back at its end, so every member stays
+ * usable through lslam_hector_* and its map through lslam_map_* between fleet calls.
+ * Every per-scan array of a call is indexed i = step * R + member: ranges row i at ranges + i * ranges_stride; n_points[i]
+ * with the containers back to back in that order; origos_xy[i][2], pose_hints[i][3], map_without_matching[i], active[i],
+ * out[i].  pose_hints NULL: every member chains from its own lastScanMatchPose.  active NULL: all 1.  A scan with
+ * active[i] == 0 is not taken: nothing of that member changes (state, planes, cached and resident container, counters), its
+ * record is all zero except n_points = -1, and in the container form its n_points[i] must be 0 -- ragged logs and robots
+ * with different scan rates.
+ * Equivalence: after a call each member's records, lslam_hector_state, planes on every level, cached and resident
+ * container are the bits lslam_hector_process_many[_points] gives on that member alone over its active scans in step
+ * order, whenever both launch the same form of the matcher.  The form follows the call's capacity (n_readings; in the
+ * container form the longest container of the whole call) and the members' common LSLAM_GN_THREADS.  A member's `scans` and
+ * `map_updates` counters advance by its active scans; its `calls` and `host_syncs` do not move: the fleet counts those.
+ * One host synchronisation per call, plus one in a ranges-form call that meets a new scan geometry (the cos / sin table,
+ * kept with member 0's map).  Inputs go up through pinned staging of the fleet's own.
+ * Members may differ in map size, cell length, offset and number of levels.
+ * LSLAM_ERR_INVALID_ARGUMENT: NULL pointers, n_members < 1, negative counts (without a device); the same processor twice, two
+ * members on one map, members of different contexts; active[i] == 0 with n_points[i] != 0.  LSLAM_ERR_UNSUPPORTED (with a
+ * message): more than 4096 members, maps created under different LSLAM_GN_THREADS, an LSLAM_MAP_OPT_ORDERED_SUMS map, more
+ * than 8 levels, more than 65536 readings or points per scan.  Nothing is enqueued by a refused call. */
+typedef struct lslam_hector_fleet lslam_hector_fleet;
+int lslam_hector_fleet_create(lslam_hector* const* members, int n_members, lslam_hector_fleet** out);
+void lslam_hector_fleet_destroy(lslam_hector_fleet* f);
+int lslam_hector_fleet_size(const lslam_hector_fleet* f);
+int lslam_hector_fleet_process_many(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_readings,
+                                    const float* ranges, int ranges_stride, const float* pose_hints,
+                                    const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out);
+int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, const float* points_xy, const int32_t* n_points,
+                                           const float* origos_xy, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out);
+/* out = {steps, member-scans processed, map updates made, calls that processed steps, waits for the stream, launches of the
+ * fleet's four kernels (copies and the clearing of an exhausted key plane are not launches of them)} */
+int lslam_hector_fleet_stats(const lslam_hector_fleet* f, int64_t out[6]);
+
+/* ---------------------------------------------------------------------------------------- */
 /* lesson5 lidar motion de-skew (LidarUndistortion::CorrectLaserScan, lesson5/src/            */
 /* lidar_undistortion.cc:339-447) -- SURVEY 8(f) #4.  Pinned (round 4) against the reference's */
 /* own source compiled in place behind ROS / tf / PCL / Eigen stand-ins (oracle/shim, which    */
