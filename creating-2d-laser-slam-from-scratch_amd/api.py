@@ -306,6 +306,8 @@ def lib() -> C.CDLL:
     L.lslam_matcher_config_defaults.argtypes = [C.POINTER(MatcherConfig)]
     L.lslam_matcher_config_defaults.restype = None
     L.lslam_matcher_create.argtypes = [vp, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
+    L.lslam_debug_reduce_lds_bytes.argtypes = [C.POINTER(MatcherConfig), i32, C.POINTER(i32 * 3)]
+    L.lslam_debug_reduce_lds_bytes.restype = i32
     L.lslam_matcher_destroy.argtypes = [vp]
     L.lslam_matcher_destroy.restype = None
     L.lslam_matcher_num_beams.argtypes = [vp]

@@ -1274,37 +1274,39 @@ constexpr int kPosChunk = 16;
 #define LSLAM_TUNE_REDUCE_NARROW_MIN 2048
 #endif
 constexpr int kReduceNarrowMinScans = LSLAM_TUNE_REDUCE_NARROW_MIN;  // batches from here on run k_reduce_coarse_lds with 128-thread blocks
-// one work item = (angle a, chunk c of 16 lattice positions) of one scan, done by one wave
+// one work item = (angle a, chunk c of CH lattice positions) of one scan, done by one wave.  The sums are integers, so
+// the chunk size changes which wave adds what and not one number; it sets how many registers the item holds (2 CH + ~30)
+template <int CH = kPosChunk>
 __device__ __forceinline__ void generic_item(const uint8_t* __restrict__ grid, const Geom& g, const PassCfg& pc,
                                              const Lattice& L, const double2* __restrict__ lp, int32_t* r, int a,
                                              int c, int lane) {
   const int np = pc.nx * pc.ny;
   const double angle = (L.center[2] - pc.ang_off) + (uint32_t)a * pc.ang_res;
   const double cosine = cos(angle), sine = sin(angle);
-  int pos[kPosChunk];
+  int pos[CH];
 #pragma unroll
-  for (int q = 0; q < kPosChunk; q++) {
-    int f = c * kPosChunk + q;
+  for (int q = 0; q < CH; q++) {
+    int f = c * CH + q;
     pos[q] = f < np ? L.gx[f % pc.nx] + L.gy[f / pc.nx] * g.stride : -1;
   }
-  int32_t acc[kPosChunk];
+  int32_t acc[CH];
 #pragma unroll
-  for (int q = 0; q < kPosChunk; q++) acc[q] = 0;
+  for (int q = 0; q < CH; q++) acc[q] = 0;
   for (int b = lane; b < g.n_beams; b += 64) {
     double2 p = lp[b];
     if (isnan(p.x)) continue;
     int t = lookup_offset(p.x, p.y, cosine, sine, g.off_x, g.off_y, g.scale, g.stride);
 #pragma unroll
-    for (int q = 0; q < kPosChunk; q++) {
+    for (int q = 0; q < CH; q++) {
       long long idx = (long long)pos[q] + t;
       if (pos[q] >= 0 && idx >= 0 && idx < g.data_size) acc[q] += grid[idx];
     }
   }
 #pragma unroll
-  for (int q = 0; q < kPosChunk; q++) {
+  for (int q = 0; q < CH; q++) {
     int v = acc[q];
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    int f = c * kPosChunk + q;
+    int f = c * CH + q;
     if (lane == 0 && f < np) r[(size_t)a * np + f] = v;
   }
 }
@@ -1328,14 +1330,15 @@ k_resp_generic(const uint8_t* __restrict__ grid, Geom g, PassCfg pc, const Latti
 // uniform -- a lattice coordinate that rounds on a cell boundary (k_pass_setup) -- and the scan's own
 // reduce block computes its numerators here before it reduces them: no work list, no extra launch.
 // `fb_step` is the lattice step the packed kernel required, or 0 when the generic kernel did the pass.
+template <int CH = kPosChunk>
 __device__ __forceinline__ void block_generic_fallback(const uint8_t* __restrict__ grid, const Geom& g,
                                                        const PassCfg& pc, const Lattice& L,
                                                        const double2* __restrict__ lp, int32_t* r, int fb_step,
                                                        int tid, int nthreads) {
   if (fb_step == 0 || (L.step_x == fb_step && L.step_y == fb_step)) return;  // block-uniform
-  const int chunks = (pc.nx * pc.ny + kPosChunk - 1) / kPosChunk;
+  const int chunks = (pc.nx * pc.ny + CH - 1) / CH;
   const int per_scan = pc.na * chunks;
-  for (int w = tid >> 6; w < per_scan; w += nthreads >> 6) generic_item(grid, g, pc, L, lp, r, w / chunks, w % chunks, tid & 63);
+  for (int w = tid >> 6; w < per_scan; w += nthreads >> 6) generic_item<CH>(grid, g, pc, L, lp, r, w / chunks, w % chunks, tid & 63);
   __syncthreads();  // the block reads these sums next
 }
 
@@ -1579,20 +1582,38 @@ k_reduce_coarse(Geom g, PassCfg pc, SearchCfg sc, const Lattice* __restrict__ la
 //  * the tie average visits only the non-zero mask words (wave ballots), still in lattice order on
 //    one thread; the ordered covariance sums stay on one thread, with their LDS reads batched.
 // ------------------------------------------------------------------------------------------
-// NT threads per block: 128 when the batch fills the chip (a block is mostly single-thread ordered sums, so residency --
-// 32 waves per CU = 16 such blocks -- buys more than lanes), 256 for small batches (latency of the one block that runs).
+// NT threads per block: 128 when the batch fills the chip (a block is mostly single-thread ordered sums, so residency
+// buys more than lanes), 256 for small batches (latency of the one block that runs).  The 128-thread form is built for
+// 8 waves per SIMD = 16 blocks per CU, and each of the three resources has to admit that: <= 64 VGPRs, <= 80 SGPRs
+// and <= 10 240 B of LDS per block, static and dynamic together (tests/test_reduce_kernel_resources.py holds all three).
+//
+// ReduceLds: the block's dynamic LDS, byte offsets for the device and the size for the host from the same numbers.
+// The work area at offset 0 is used twice: [dpen: 1 double per lattice cell][latmax: `parts` per cell] until the ties
+// are marked, then `terms` (4 per cell) -- every read of dpen and latmax is behind the barriers in front of its writes.
+struct ReduceLds {
+  int probs, mask, cell, tie, bytes;
+  __host__ __device__ ReduceLds(int ncand, int na, int probs_side, int parts) {
+    const int words = (ncand * na + 31) / 32;
+    probs = (1 + parts > 4 ? 1 + parts : 4) * ncand * 8;
+    mask = probs + probs_side * probs_side * 8;
+    cell = mask + words * 4;
+    tie = cell + ncand * 4;
+    bytes = tie + ncand * 4 + 16;
+  }
+};
+constexpr int kReduceNarrowChunk = 4;  // positions per item of the 128-thread form's own generic fallback (generic_item)
 // The block's work as a function of (scan s, thread tid of NT): `r` = the scan's numerators (angle-major: global in
-// k_reduce_coarse_lds, the block's LDS copy in k_match_step), `smem` = reduce_lds_nocache() bytes of LDS scratch.
+// k_reduce_coarse_lds, the block's LDS copy in k_match_step), `smem` = ReduceLds::bytes of LDS scratch.
 template <int NT>
 __device__ __forceinline__ void reduce_coarse_lds_block(
     const int s, const int tid, const Geom& g, const PassCfg& pc, const SearchCfg& sc, Lattice* lat, int32_t* r,
     CoarseOut* __restrict__ out, int use_expansion, int pass_index, const uint8_t* __restrict__ grid,
     const double2* __restrict__ local, int fb_step, const PassCfg& fine_pc, double2* fine_cossin, int fine_step,
     int zero_fine_words, int parts, unsigned char* smem) {
-  __shared__ double sh[NT];
+  __shared__ double sh[NT / 64];  // block_max: one slot per wave
   __shared__ double s_ap[kMaxAngles];
   __shared__ unsigned long long s_nz[4];
-  __shared__ double s_avg[3];
+  __shared__ double s_avg[3], s_best;
   __shared__ int s_status, s_bad, s_ntie, s_wcnt[(NT + 63) / 64];
   const Lattice& L = lat[s];
   if (!L.active) return;
@@ -1601,7 +1622,9 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
     return;
   }
   LSLAM_PHASE_CLOCK(pck);
-  block_generic_fallback(grid, g, pc, L, local + (size_t)s * g.n_beams, r, fb_step, tid, NT);
+  // (rare, and the block's register peak: the narrow form walks it in chunks of 4 positions, not 16 -- same sums)
+  block_generic_fallback<NT == 128 ? kReduceNarrowChunk : kPosChunk>(grid, g, pc, L, local + (size_t)s * g.n_beams, r, fb_step,
+                                                                     tid, NT);
   const int ncand = pc.nx * pc.ny;
   const int total = ncand * pc.na;
   const int words = (total + 31) / 32;  // <= 256 (host)
@@ -1609,13 +1632,15 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
   // kernel is latency-bound, so residency is what it needs): each thread owns the angles of ONE lattice cell half and
   // keeps only the cell maximum; the few cells that can tie with the best response are re-evaluated below with the
   // same expression, hence the same bits.
-  double* latmax = (double*)smem;  // `parts` rows of ncand: the angles of a cell are split over `parts` threads (host:
-  double* probs = latmax + (size_t)parts * ncand;  // as many as fit the block, so that a thread's loads are one batch)
-  double* terms = probs + g.probs_side * g.probs_side;  // 4 per lattice cell
-  uint32_t* mask = (uint32_t*)(terms + 4 * ncand);
-  int* cell = (int*)(mask + words);
-  int* tie = cell + ncand;  // lattice cells that may hold a tie with the best response
-  double* dpen = terms;  // distance penalty per lattice cell; dead before `terms` is written
+  const ReduceLds lds(ncand, pc.na, g.probs_side, parts);
+  double* dpen = (double*)smem;    // distance penalty per lattice cell; dead before `terms` is written
+  double* latmax = dpen + ncand;   // `parts` rows of ncand: the angles of a cell are split over `parts` threads (host:
+                                   // as many as fit the block, so that a thread's loads are one batch); dead likewise
+  double* terms = (double*)smem;   // 4 per lattice cell
+  double* probs = (double*)(smem + lds.probs);
+  uint32_t* mask = (uint32_t*)(smem + lds.mask);
+  int* cell = (int*)(smem + lds.cell);
+  int* tie = (int*)(smem + lds.tie);  // lattice cells that may hold a tie with the best response
   const double center[3] = {L.center[0], L.center[1], L.center[2]};
 
   // per-cell and per-angle penalty factors (Mapper.cpp:399-414) + search-space cell of every lattice
@@ -1660,7 +1685,10 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
 #if !defined(LSLAM_TUNE_REDUCE_BATCH)
 #define LSLAM_TUNE_REDUCE_BATCH 11
 #endif
-    constexpr int kBatch = LSLAM_TUNE_REDUCE_BATCH;
+#if !defined(LSLAM_TUNE_REDUCE_BATCH_NARROW)
+#define LSLAM_TUNE_REDUCE_BATCH_NARROW 7  // the 128-thread form: 21 angles = 7 + 7 + 7; eleven divisions in flight do not fit 64 VGPRs
+#endif
+    constexpr int kBatch = NT == 128 ? LSLAM_TUNE_REDUCE_BATCH_NARROW : LSLAM_TUNE_REDUCE_BATCH;
     for (int a0 = a_lo; a0 < a_hi; a0 += kBatch) {
       int32_t rv[kBatch];
 #pragma unroll
@@ -1676,7 +1704,7 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
     lm = lm > m ? lm : m;
   }
   LSLAM_PHASE_MARK(pck, 1);  // numerators -> penalised responses (one division each), cell maxima
-  const double best = block_max(lm, sh, tid, NT);  // contains the barriers that publish the latmax rows
+  const double best0 = block_max(lm, sh, tid, NT);  // contains the barriers that publish the latmax rows
   LSLAM_PHASE_MARK(pck, 2);  // block maximum
 
   // best response per lattice cell over all angles, max-merged into the search-space probabilities
@@ -1688,12 +1716,12 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
     if (cell[c] < 0) s_bad = 1;
     else atomicMax((unsigned long long*)&probs[cell[c]], (unsigned long long)__double_as_longlong(m < 0.0 ? 0.0 : m));
     // ties with the best response (:452-455): only a cell whose maximum reaches it can hold one
-    if (!(m + 2.0 * kTol < best)) tie[atomicAdd(&s_ntie, 1)] = c;  // conservative filter; the test below is the reference's
+    if (!(m + 2.0 * kTol < best0)) tie[atomicAdd(&s_ntie, 1)] = c;  // conservative filter; the test below is the reference's
   }
   __syncthreads();
   for (int idx = tid, n = s_ntie * pc.na; idx < n; idx += NT) {
     const int c = tie[idx / pc.na], a = idx % pc.na;
-    if (double_equal(value_of(r[a * ncand + c], c, a), best)) {
+    if (double_equal(value_of(r[a * ncand + c], c, a), best0)) {
       const int k = c * pc.na + a;
       atomicOr(&mask[k >> 5], 1u << (k & 31));
     }
@@ -1708,6 +1736,7 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
   LSLAM_PHASE_MARK(pck, 3);  // probabilities merged, tie candidates re-evaluated, mask words
   if (tid == 0) {
     LSLAM_SERIAL_BEGIN();
+    s_best = best0;  // read back where it is needed again: it would sit in two registers through everything below
     int st = s_bad ? LSLAM_ERR_PROBABILITY_SEARCH : 0;
     double avg[3] = {0, 0, 0};
     if (st == 0) {  // tie average in lattice order (Mapper.cpp:456-483), only over the words that hold ties
@@ -1758,7 +1787,7 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
   // response >= best - 0.1 enter the sums (:580): they are compacted IN LATTICE ORDER (wave ballots), so the one thread
   // that adds them up in the reference's order walks a dozen entries instead of every cell of the lattice.
   const double dx = s_avg[0] - center[0], dy = s_avg[1] - center[1];
-  const double thr = best - 0.1;
+  const double thr = s_best - 0.1;
   int n_pass = 0;
   for (int c0 = 0; c0 < ncand; c0 += NT) {
     const int c = c0 + tid;
@@ -1789,6 +1818,7 @@ __device__ __forceinline__ void reduce_coarse_lds_block(
   LSLAM_PHASE_MARK(pck, 5);  // fine lattice (last wave) | covariance terms compacted in lattice order
   if (tid == 0) {
     CoarseOut o;
+    const double best = s_best;
     o.status = s_status;
     o.flags = pass_index > 0 ? 1 : 0;
     o.pad = 0;
@@ -1846,7 +1876,7 @@ struct SpecArgs {
 };
 __device__ __forceinline__ void anchor_spec_block(int n, const SpecArgs& sa, const Geom& g, unsigned char* smem);
 template <int NT>
-__global__ void __launch_bounds__(NT)
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 128 ? 8 : NT / 256 > 0 ? NT / 256 : 1, 8)))
 k_reduce_coarse_lds(Geom g, PassCfg pc, SearchCfg sc, Lattice* lat,
                     int32_t* resp, size_t resp_stride, CoarseOut* __restrict__ out,
                     int use_expansion, int pass_index, const uint8_t* __restrict__ grid,
@@ -3756,19 +3786,22 @@ int wait_record(lslam_matcher* m) {
 int n_angles_of(double off, double res) { return lattice_count(off, res); }
 
 // coarse pass geometry (Mapper.cpp:228-240)
-PassCfg coarse_pass_cfg(const lslam_matcher* m, const Geom& g) {
+PassCfg coarse_pass_cfg(const lslam_matcher_config& cfg, const Geom& g) {
   const double res = 1.0 / g.scale;  // GetResolution() (Karto.h:4335-4338)
   PassCfg pc;
   pc.off_x = pc.off_y = 0.5 * ((double)g.probs_side - 1) * res;
   pc.res_x = pc.res_y = 2 * res;
-  pc.ang_off = m->cfg.coarse_search_angle_offset;
-  pc.ang_res = m->cfg.coarse_angle_resolution;
+  pc.ang_off = cfg.coarse_search_angle_offset;
+  pc.ang_res = cfg.coarse_angle_resolution;
   pc.nx = lattice_count(pc.off_x, pc.res_x);
   pc.ny = lattice_count(pc.off_y, pc.res_y);
   pc.na = n_angles_of(pc.ang_off, pc.ang_res);
   pc.mode = 0;
   return pc;
 }
+PassCfg coarse_pass_cfg(const lslam_matcher* m, const Geom& g) { return coarse_pass_cfg(m->cfg, g); }
+// k_reduce_coarse_lds: threads of a block that share the angles of one lattice cell
+int reduce_parts_of(int ncand, int nt) { return std::max(1, std::min(8, nt / ncand)); }
 
 template <typename RT>
 int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, const double* d_poses,
@@ -3929,10 +3962,9 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
            ((total + 31) / 32) * 4 + 16;
   };
   // k_reduce_coarse_lds keeps no per-candidate cache: two cell-maximum arrays instead
-  auto reduce_parts = [&](const PassCfg& p, int nt) -> int { return std::max(1, std::min(8, nt / (p.nx * p.ny))); };
+  auto reduce_parts = [&](const PassCfg& p, int nt) -> int { return reduce_parts_of(p.nx * p.ny, nt); };
   auto reduce_lds_nocache = [&](const PassCfg& p, int parts) -> size_t {
-    size_t total = (size_t)p.nx * p.ny * p.na;
-    return (size_t)p.nx * p.ny * (8 * parts + 32 + 4 + 4) + (size_t)g.probs_side * g.probs_side * 8 + ((total + 31) / 32) * 4 + 16;
+    return (size_t)ReduceLds(p.nx * p.ny, p.na, g.probs_side, parts).bytes;
   };
   // response numerators of one pass: packed row kernel for uniform lattices (step 2 on the parity
   // planes, step 1 on the grid), generic kernel for everything else
@@ -4577,6 +4609,16 @@ void lslam_robot_pose_from_sensor(const lslam_laser* l, const double sensor[3], 
   robot[0] = sensor[0] - wx;
   robot[1] = sensor[1] - wy;
   robot[2] = normalize_angle(sensor[2] - l->offset_heading);
+}
+
+int lslam_debug_reduce_lds_bytes(const lslam_matcher_config* cfg, int threads, int dims[3]) {
+  if (!cfg || !(cfg->resolution > 0.0) || (threads != 128 && threads != 256 && threads != 1024)) return -1;
+  Geom g{};
+  g.scale = 1.0 / cfg->resolution;
+  g.probs_side = (int)(uint32_t)(kround(cfg->search_size / cfg->resolution) + 1);  // as lslam_matcher_create
+  const PassCfg pc = coarse_pass_cfg(*cfg, g);
+  if (dims) { dims[0] = pc.nx; dims[1] = pc.ny; dims[2] = pc.na; }
+  return ReduceLds(pc.nx * pc.ny, pc.na, g.probs_side, reduce_parts_of(pc.nx * pc.ny, threads)).bytes;
 }
 
 int lslam_matcher_create(lslam_context* ctx, const lslam_matcher_config* cfg, const lslam_laser* laser,

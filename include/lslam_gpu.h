@@ -235,6 +235,10 @@ int lslam_matcher_coarse_form_launches(const lslam_matcher* m, int64_t out[LSLAM
 /* diagnostics: k_match_lone's hand-over words, 16 slots x 8 words {coarse tickets, coarse done, fine ready, fine tickets,
  * fine done, timeouts, 0, 0}; LSLAM_ERR_NO_DATA before the first such launch */
 int lslam_debug_lone_sync(lslam_matcher* m, unsigned* out128);
+/* diagnostics, no device needed: the dynamic LDS bytes one block of the coarse reduce (k_reduce_coarse_lds) is launched with
+ * for this configuration's coarse lattice, in its 128-, 256- or 1024-thread form; dims (optional) = the lattice {nX, nY, nA}.
+ * Together with the kernel's static LDS this is what decides how many blocks a CU holds.  -1 for anything else. */
+int lslam_debug_reduce_lds_bytes(const lslam_matcher_config* cfg, int threads, int dims[3]);
 int lslam_matcher_set_option(lslam_matcher* m, int option, int value);
 int lslam_matcher_read_stats(lslam_matcher* m, uint64_t out[4]);
 /* after an instrumented pass: out[0] = readable (scan, beam) pairs of that batch, out[1] = those with a live lattice row in
