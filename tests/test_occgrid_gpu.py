@@ -34,6 +34,9 @@ def test_create_from_scans_matches_oracle(ctx, oracle_lib, res, thr, n_scans):
     assert np.array_equal(got, exp)
     ros = g.ros_data()
     assert np.array_equal(ros == -1, exp == 0) and np.array_equal(ros == 100, exp == 100) and np.array_equal(ros == 0, exp == 255)
+    # the counters behind the cells, word for word: a pass count one off classifies the same almost everywhere
+    dims, cnt = port.occgrid_partial(ranges, wl.base_poses, res, port.occgrid_bounds(ranges, wl.base_poses))
+    assert (dims[0], dims[1]) == (w, h) and np.array_equal(g.export_counters(), cnt)
 
 
 def test_no_scans_is_null(ctx):
