@@ -363,6 +363,11 @@ def lib() -> C.CDLL:
     L.lslam_occgrid_import_counters.argtypes = [vp, vp, i32, i32]
     L.lslam_occgrid_counters_dev_ptr.restype = vp
     L.lslam_occgrid_counters_dev_ptr.argtypes = [vp]
+    L.lslam_occgrid_ray_cast.argtypes = [vp, i32, vp, vp, dbl, vp]
+    L.lslam_occgrid_ray_cast_dev.argtypes = [vp, i32, vp, vp, dbl, vp]
+    L.lslam_occgrid_ray_cast_scans.argtypes = [vp, C.POINTER(LaserParams), i32, vp, dbl, vp, i32]
+    L.lslam_occgrid_ray_cast_scans_dev.argtypes = [vp, C.POINTER(LaserParams), i32, vp, dbl, vp, i32]
+    L.lslam_occgrid_ray_cast_stats.argtypes = [vp, vp]
     L.lslam_occgrid_create_sharded.argtypes = [vp, C.POINTER(LaserParams), i32, vp, i32, vp, dbl, vp, C.POINTER(vp)]
     L.lslam_pool_occgrid_from_scans.argtypes = [vp, C.POINTER(LaserParams), i32, vp, i32, vp, dbl, C.POINTER(vp)]
     L.lslam_frontend_livemap_create.argtypes = [vp, dbl, C.POINTER(vp)]
@@ -1179,6 +1184,55 @@ class OccupancyGrid:
         out = np.zeros((h, w), dtype=np.int8)
         self.ctx.check(self.L.lslam_occgrid_read_ros_i8(self.h, out.ctypes.data))
         return out
+
+    # ---- OccupancyGrid::RayCast (Karto.h:5717-5755), batched ----
+    @staticmethod
+    def laser_beams(laser: LaserParams) -> int:
+        """The beam count the library derives from a laser: (kt_int32u)Round((max - min) / resolution)."""
+        v = (laser.maximum_angle - laser.minimum_angle) / laser.angular_resolution
+        return int(math.floor(v + 0.5) if v >= 0.0 else math.ceil(v - 0.5))
+
+    def ray_cast(self, poses, max_range) -> np.ndarray:
+        """Distance from every pose (x, y, heading) along its heading to the first cell that is not free, at most
+        max_range (a scalar for all rays, or one value per ray).  -> float64 [n]"""
+        p = _f64(poses).reshape(-1, 3)
+        out = np.zeros(p.shape[0])
+        if np.ndim(max_range) == 0:
+            mr, common = None, float(max_range)
+        else:
+            mr, common = _f64(max_range).reshape(-1), 0.0
+            if mr.size != p.shape[0]:
+                raise ValueError(f"expected {p.shape[0]} max ranges, got {mr.size}")
+        self.ctx.check(self.L.lslam_occgrid_ray_cast(self.h, p.shape[0], p.ctypes.data, None if mr is None else mr.ctypes.data,
+                                                     common, out.ctypes.data))
+        return out
+
+    def ray_cast_scans(self, laser: LaserParams, sensor_poses, max_range: float, out_stride: int | None = None) -> np.ndarray:
+        """The range image `laser` would see from every sensor pose: beam i looks along heading + minimum_angle +
+        i * angular_resolution.  -> float64 [n_poses, out_stride] (out_stride defaults to the beam count; columns past it
+        are left zero), the layout match_batch and the front-end take as ranges."""
+        p = _f64(sensor_poses).reshape(-1, 3)
+        stride = self.laser_beams(laser) if out_stride is None else int(out_stride)
+        out = np.zeros((p.shape[0], max(stride, 0)))
+        self.ctx.check(self.L.lslam_occgrid_ray_cast_scans(self.h, C.byref(laser), p.shape[0], p.ctypes.data, float(max_range),
+                                                           out.ctypes.data, stride))
+        return out
+
+    def ray_cast_dev(self, n_rays: int, poses_ptr: int, max_ranges_ptr: int | None, max_range: float, out_ptr: int):
+        """ray_cast on device pointers: enqueued on the context stream, no host wait (results after ctx.synchronize())."""
+        self.ctx.check(self.L.lslam_occgrid_ray_cast_dev(self.h, int(n_rays), C.c_void_p(poses_ptr),
+                                                         C.c_void_p(max_ranges_ptr) if max_ranges_ptr else None,
+                                                         float(max_range), C.c_void_p(out_ptr)))
+
+    def ray_cast_scans_dev(self, laser: LaserParams, n_poses: int, poses_ptr: int, max_range: float, out_ptr: int,
+                           out_stride: int):
+        self.ctx.check(self.L.lslam_occgrid_ray_cast_scans_dev(self.h, C.byref(laser), int(n_poses), C.c_void_p(poses_ptr),
+                                                               float(max_range), C.c_void_p(out_ptr), int(out_stride)))
+
+    def ray_cast_stats(self) -> dict:
+        out = np.zeros(4, dtype=np.int64)
+        self.ctx.check(self.L.lslam_occgrid_ray_cast_stats(self.h, out.ctypes.data))
+        return dict(zip(("calls", "rays", "refreshes", "samples"), (int(v) for v in out)))
 
 
 class _OccupancyGridView(OccupancyGrid):

@@ -254,6 +254,7 @@ int live_update(lslam_livemap* lm) {
   og->d_hit = og->d_pass + std::max<size_t>(cells, 1);
   og->cells = cells;
   og->g = g;
+  og->counters_written();  // new planes, a new geometry or new traces: every path below this line changes the map
   if (rebuild) LSLAM_HIP(ctx, hipMemsetAsync(og->d_pass, 0, words * sizeof(uint32_t), ctx->stream));
   const int K = N - first;
   if (n > 0 && cells > 0) {

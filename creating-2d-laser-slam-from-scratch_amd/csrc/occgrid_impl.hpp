@@ -48,6 +48,15 @@ inline OccGeom occ_geom(const double bbox[4], double resolution) {
   return g;
 }
 
+// UpdateCell (Karto.h:5950-5965) of one cell from its two counters: MinPassThrough = 2, OccupancyThreshold = 0.1
+// (:5636-5637).  GridStates (Karto.h:4193-4198): 0 unknown, 100 occupied, 255 free.  The ONE statement of the cell rule:
+// the published map (k_occ_update) and the ray cast's cell plane (raycast.hip) both apply it.
+__device__ __forceinline__ uint8_t occ_cell_state(uint32_t pc, uint32_t hc) {
+  uint8_t v = 0;  // GridStates_Unknown
+  if (pc > 2u) v = ((double)hc / (double)pc > 0.1) ? 100 : 255;
+  return v;
+}
+
 // RayTrace (Karto.h:5907-5942) of one beam by one wave (`lane` = 0..63), cells (x0, y0) -> (x1, y1).
 // Grid<T>::TraceLine (Karto.h:4680-4745) in closed form: with deltaY <= deltaX the error recurrence
 // "error += deltaY; if (2*error >= deltaX) { y += ystep; error -= deltaX; }" has taken
@@ -91,6 +100,10 @@ int frontend_view(lslam_frontend* f, FrontendView* v);
 // reports, as the reference's scans derive theirs), 3 doubles each
 void frontend_sensor_poses(const lslam_frontend* f, int first, int count, double* out);
 
+// ---- what the ray cast keeps in a grid handle (raycast.hip) ----
+struct RayCastState;
+void raycast_release(lslam_occgrid* og);  // frees og->rc and takes its hook off the context (lslam_occgrid_destroy)
+
 }  // namespace lslam
 
 struct lslam_occgrid {
@@ -100,4 +113,14 @@ struct lslam_occgrid {
   uint32_t* d_hit = nullptr;
   size_t cells = 0;            // stride * h words per plane
   lslam::DevBuf<uint8_t> d_out;
+  // Whoever changes the counters, the planes they live in or the geometry says so HERE, and nowhere else: whatever is
+  // derived from the counters and kept (the ray cast's cell plane) compares the epoch it was derived at with this one.
+  // Writers take the planes from planes_for_write(), which says it for them.
+  uint64_t counters_epoch = 1;
+  void counters_written() { counters_epoch++; }
+  uint32_t* planes_for_write() {
+    counters_written();
+    return d_pass;
+  }
+  lslam::RayCastState* rc = nullptr;  // created by the first ray cast
 };

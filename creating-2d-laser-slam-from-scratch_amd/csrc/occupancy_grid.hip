@@ -114,8 +114,7 @@ k_occ_update(OccGeom g, const uint32_t* __restrict__ pass, const uint32_t* __res
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= g.w || y >= g.h) return;
   const uint32_t pc = pass[x + (size_t)y * g.stride], hc = hit[x + (size_t)y * g.stride];
-  uint8_t v = 0;  // GridStates_Unknown
-  if (pc > 2u) v = ((double)hc / (double)pc > 0.1) ? 100 : 255;
+  uint8_t v = occ_cell_state(pc, hc);
   if (ros) v = v == 0 ? (uint8_t)(int8_t)-1 : (v == 100 ? 100 : 0);
   out[(size_t)y * g.w + x] = v;
 }
@@ -197,7 +196,7 @@ int occ_build(lslam_context* ctx, const lslam_laser* laser, int n_scans, const d
   }
   og->d_hit = og->d_pass + std::max<size_t>(cells, 1);
   og->cells = cells;
-  (void)hipMemsetAsync(og->d_pass, 0, std::max<size_t>(cells, 1) * 8, ctx->stream);
+  (void)hipMemsetAsync(og->planes_for_write(), 0, std::max<size_t>(cells, 1) * 8, ctx->stream);
   if (n > 0 && n_scans > 0 && cells > 0) {
     const long long beams = (long long)n_scans * n;
     launch(ctx, "occ_trace", k_occ_trace, dim3((unsigned)((beams + 3) / 4)), dim3(256), 0, n_scans, l,
@@ -254,7 +253,8 @@ int lslam_occgrid_counter_words(const lslam_occgrid* og, size_t* words) {
   return LSLAM_OK;
 }
 
-void* lslam_occgrid_counters_dev_ptr(lslam_occgrid* og) { return og ? (void*)og->d_pass : nullptr; }
+// the caller writes through it (an in-place all-reduce): handing it out counts as a write
+void* lslam_occgrid_counters_dev_ptr(lslam_occgrid* og) { return og ? (void*)og->planes_for_write() : nullptr; }
 
 int lslam_occgrid_export_counters(lslam_occgrid* og, uint32_t* out, int on_device) {
   if (!og || (!out && og->cells)) return LSLAM_ERR_INVALID_ARGUMENT;
@@ -274,7 +274,7 @@ int lslam_occgrid_import_counters(lslam_occgrid* og, const uint32_t* in, int on_
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
   const size_t words = 2 * og->cells;
   if (!accumulate) {
-    LSLAM_HIP(ctx, hipMemcpyAsync(og->d_pass, in, words * sizeof(uint32_t),
+    LSLAM_HIP(ctx, hipMemcpyAsync(og->planes_for_write(), in, words * sizeof(uint32_t),
                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
   } else {
     const uint32_t* src = in;
@@ -284,7 +284,7 @@ int lslam_occgrid_import_counters(lslam_occgrid* og, const uint32_t* in, int on_
       LSLAM_HIP(ctx, hipMemcpyAsync(staged.p, in, words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
       src = staged.p;
     }
-    launch(ctx, "occ_add", k_occ_add, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, og->d_pass, src, words);
+    launch(ctx, "occ_add", k_occ_add, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, og->planes_for_write(), src, words);
     hipError_t e = hipStreamSynchronize(ctx->stream);
     staged.release();
     if (e != hipSuccess) return ctx->fail(LSLAM_ERR_HIP, "counter merge failed: %s", hipGetErrorString(e));
@@ -297,6 +297,7 @@ int lslam_occgrid_import_counters(lslam_occgrid* og, const uint32_t* in, int on_
 void lslam_occgrid_destroy(lslam_occgrid* og) {
   if (!og) return;
   (void)hipStreamSynchronize(og->ctx->stream);
+  raycast_release(og);
   if (og->d_pass) (void)hipFree(og->d_pass);
   og->d_out.release();
   delete og;

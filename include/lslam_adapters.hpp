@@ -259,6 +259,68 @@ class LiveOccupancyGrid {
   double off_[2] = {0.0, 0.0};
 };
 
+// karto::OccupancyGrid::RayCast (Karto.h:5717-5755) over a map that lives on the device: the distance from a pose along
+// its heading to the first cell that is not free, at most maxRange.  Borrows an lslam_occgrid -- one built by
+// lslam_occgrid_create_* or the live map's (LiveOccupancyGrid::Grid(), valid until its next Update) -- and never
+// releases it.  RayCast is the reference's call with plain doubles; RayCastMany and RayCastScans are what a localiser or
+// a scan synthesiser wants: many rays, or whole range images, per call.
+class OccupancyGridRayCaster {
+ public:
+  OccupancyGridRayCaster(lslam_context* ctx, lslam_occgrid* grid) : ctx_(ctx), og_(grid) {}
+
+  // RayCast(Pose2(x, y, heading), maxRange)
+  double RayCast(double x, double y, double heading, double maxRange) const {
+    const double pose[3] = {x, y, heading};
+    double d = 0.0;
+    Check(lslam_occgrid_ray_cast(og_, 1, pose, nullptr, maxRange, &d));
+    return d;
+  }
+  // poses: (x, y, heading) per ray; one maxRange for all of them
+  std::vector<double> RayCastMany(const std::vector<Pose2>& poses, double maxRange) const {
+    std::vector<double> xyh(poses.size() * 3), out(poses.size());
+    for (size_t i = 0; i < poses.size(); i++) { xyh[3 * i] = poses[i].x; xyh[3 * i + 1] = poses[i].y; xyh[3 * i + 2] = poses[i].heading; }
+    Check(lslam_occgrid_ray_cast(og_, static_cast<int>(poses.size()), xyh.data(), nullptr, maxRange, out.data()));
+    return out;
+  }
+  // ... or one per ray
+  std::vector<double> RayCastMany(const std::vector<Pose2>& poses, const std::vector<double>& maxRanges) const {
+    if (maxRanges.size() != poses.size()) throw std::invalid_argument("lslam: one max range per ray");
+    std::vector<double> xyh(poses.size() * 3), out(poses.size());
+    for (size_t i = 0; i < poses.size(); i++) { xyh[3 * i] = poses[i].x; xyh[3 * i + 1] = poses[i].y; xyh[3 * i + 2] = poses[i].heading; }
+    Check(lslam_occgrid_ray_cast(og_, static_cast<int>(poses.size()), xyh.data(), maxRanges.data(), 0.0, out.data()));
+    return out;
+  }
+  // The range image `laser` sees from every SENSOR pose: beam i looks along heading + minimum_angle + i * angular_resolution
+  // (Karto.h:5394).  Row-major [poses][numBeams] -- the `ranges` layout GpuScanMatcher and GpuFrontEnd take; numBeams is set
+  // to the laser's beam count.
+  std::vector<double> RayCastScans(const lslam_laser& laser, const std::vector<Pose2>& sensorPoses, double maxRange,
+                                   int* numBeams = nullptr) const {
+    const double v = (laser.maximum_angle - laser.minimum_angle) / laser.angular_resolution;  // Karto.h:4152-4161
+    const int n = static_cast<int>(v >= 0.0 ? std::floor(v + 0.5) : std::ceil(v - 0.5));
+    if (numBeams) *numBeams = n;
+    std::vector<double> xyh(sensorPoses.size() * 3), out(sensorPoses.size() * static_cast<size_t>(n > 0 ? n : 0));
+    for (size_t i = 0; i < sensorPoses.size(); i++) {
+      xyh[3 * i] = sensorPoses[i].x; xyh[3 * i + 1] = sensorPoses[i].y; xyh[3 * i + 2] = sensorPoses[i].heading;
+    }
+    Check(lslam_occgrid_ray_cast_scans(og_, &laser, static_cast<int>(sensorPoses.size()), xyh.data(), maxRange, out.data(), n));
+    return out;
+  }
+  // calls, rays, cell-plane refreshes, samples tested
+  std::vector<int64_t> Stats() const {
+    std::vector<int64_t> s(4, 0);
+    lslam_occgrid_ray_cast_stats(og_, s.data());
+    return s;
+  }
+  lslam_occgrid* Grid() const { return og_; }
+
+ private:
+  void Check(int rc) const {
+    if (rc != LSLAM_OK) throw MatcherError(rc, lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_occgrid* og_;
+};
+
 // Batched many-scan mode over every GPU of the node (one process): scans sharded [r*B/W, (r+1)*B/W), shared grid
 // replicated over xGMI, results in scan order
 class GpuMatcherPool {

@@ -501,7 +501,8 @@ int lslam_occgrid_create_partial(lslam_context* ctx, const lslam_laser* laser, i
                                  lslam_occgrid** out);
 int lslam_occgrid_counter_words(const lslam_occgrid* og, size_t* words);
 /* device address of the counter buffer (pass plane, then hit plane; lslam_occgrid_counter_words uint32 words): a caller
- * with its own RCCL communicator all-reduces it in place */
+ * with its own RCCL communicator all-reduces it in place.  Handing it out counts as a write of the counters: a caller
+ * that writes through it again later asks for it again before the next ray cast. */
 void* lslam_occgrid_counters_dev_ptr(lslam_occgrid* og);
 int lslam_occgrid_export_counters(lslam_occgrid* og, uint32_t* buf, int on_device);
 int lslam_occgrid_import_counters(lslam_occgrid* og, const uint32_t* buf, int on_device, int accumulate);
@@ -541,6 +542,43 @@ lslam_occgrid* lslam_livemap_grid(lslam_livemap* lm);
 /* out[6] = updates, of those appends (box unchanged: new scans traced), grows (a max side moved: rows copied to the new
  * stride, new scans traced, old scans re-traced for the cells the old bounds clipped), rebuilds (everything retraced); scans traced summed over all updates; scans in the map */
 int lslam_livemap_stats(const lslam_livemap* lm, int64_t out[6]);
+
+/* Ray cast: karto::OccupancyGrid::RayCast(const Pose2&, kt_double maxRange) (Karto.h:5717-5755), batched -- the distance
+ * from a pose along its heading to the first cell that is not FREE, in the reference's fp64 expression order:
+ *     steps = max(1 + |maxRange cos h| / res, 1 + |maxRange sin h| / res), delta = maxRange / steps; sample i = 1, 2, ...
+ *     (while i < steps) lies i * delta away; the first sample outside the grid or on a cell that is not free (unknown
+ *     cells stop a ray like occupied ones) ends the ray at i * delta; a ray that runs out returns maxRange.  The start
+ *     cell itself is never tested.
+ * Rays read the cell states lslam_occgrid_read_u8 reports; the grid keeps them as a byte plane in HBM that is derived
+ * again only when the counters have changed since the last cast (create, import_counters, a live-map update, handing
+ * out lslam_occgrid_counters_dev_ptr).  Every entry point works on the borrowed grid of lslam_livemap_grid.
+ *   lslam_occgrid_ray_cast        n_rays poses (x, y, heading), 3 doubles each; max_ranges[n_rays], or NULL: the common
+ *                                 max_range for every ray; out[n_rays].  (Karto.h:5717-5755)
+ *   lslam_occgrid_ray_cast_scans  n_poses SENSOR poses x the beams of `laser` (its beam count as everywhere else in this
+ *                                 library): beam i has heading pose.heading + minimum_angle + i * angular_resolution,
+ *                                 evaluated left to right (Karto.h:5394), and is cast as above (Karto.h:5717-5755).
+ *                                 out_ranges[n_poses][out_stride], out_stride >= beams: the layout lslam_matcher_match_batch
+ *                                 and the front-end take as `ranges`.  Bit-identical to lslam_occgrid_ray_cast fed those
+ *                                 headings.
+ * The host entry points are synchronous.  The _dev ones take device pointers, enqueue on the context stream and do
+ * not wait; nothing is allocated for a repeated shape.  (Karto.h:5717-5755)
+ * LSLAM_ERR_INVALID_ARGUMENT: NULL pointers, negative counts, out_stride below the beam count, a common max_range that
+ * is not a positive finite number (all without a device).  LSLAM_ERR_UNSUPPORTED: a ray the reference itself cannot
+ * finish -- its `steps` does not fit the reference's uint32 counter, its stopping sample's grid coordinate does not fit
+ * int32, or its per-ray max_range is not a positive finite number.  That is found on the device: such a ray's output
+ * is NaN, every other ray's is valid, and the error is returned by the host entry point, or by the next
+ * lslam_synchronize after a _dev one. */
+int lslam_occgrid_ray_cast(lslam_occgrid* og, int n_rays, const double* poses_xyh, const double* max_ranges /* NULL: common */,
+                           double max_range, double* out_host);
+int lslam_occgrid_ray_cast_dev(lslam_occgrid* og, int n_rays, const double* d_poses_xyh, const double* d_max_ranges,
+                               double max_range, double* d_out);
+int lslam_occgrid_ray_cast_scans(lslam_occgrid* og, const lslam_laser* laser, int n_poses, const double* sensor_poses,
+                                 double max_range, double* out_ranges_host, int out_stride);
+int lslam_occgrid_ray_cast_scans_dev(lslam_occgrid* og, const lslam_laser* laser, int n_poses, const double* d_sensor_poses,
+                                     double max_range, double* d_out_ranges, int out_stride);
+/* out[4] = calls, rays, cell-plane refreshes, samples tested (what the loop of Karto.h:5717-5755 would have tested: the
+ * stopping index of a stopped ray, every sample of one that ran out).  Waits for the context stream. */
+int lslam_occgrid_ray_cast_stats(const lslam_occgrid* og, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Hector log-odds occupancy grid  (replaces hectorslam::OccGridMapBase<LogOddsCell,...>,    */

@@ -40,8 +40,14 @@ inline lslam_laser LaserFrom(karto::LaserRangeFinder* lrf) {
   return l;
 }
 
+// The build itself.  ppDeviceGrid == NULL: the device grid is released once its cells are on the host (the function the
+// call site swaps in, below).  Otherwise *ppDeviceGrid is the live lslam_occgrid the host grid was read from: the caller
+// keeps QUERYING the map on the device -- lslam_occgrid_ray_cast* / lslam::OccupancyGridRayCaster, which answer
+// OccupancyGrid::RayCast (Karto.h:5717-5755) for thousands of poses per call without another read-back -- and releases it
+// with lslam_occgrid_destroy.
 inline karto::OccupancyGrid* CreateOccupancyGridFromScans(lslam_context* ctx, const karto::LocalizedRangeScanVector& rScans,
-                                                          kt_double resolution) {
+                                                          kt_double resolution, lslam_occgrid** ppDeviceGrid) {
+  if (ppDeviceGrid) *ppDeviceGrid = NULL;
   if (rScans.empty()) return NULL;  // Karto.h:5661-5664
   if (karto::math::DoubleEqual(resolution, 0.0)) throw karto::Exception("Resolution cannot be 0");  // the ctor's check (:5627-5630)
   karto::LaserRangeFinder* lrf = rScans[0]->GetLaserRangeFinder();
@@ -71,13 +77,19 @@ inline karto::OccupancyGrid* CreateOccupancyGridFromScans(lslam_context* ctx, co
   lslam_occgrid_info(og, dims, off, &res);
   std::vector<uint8_t> cells(static_cast<size_t>(dims[0]) * dims[1]);
   rc = lslam_occgrid_read_u8(og, cells.data());
-  lslam_occgrid_destroy(og);
+  if (rc != LSLAM_OK || !ppDeviceGrid) lslam_occgrid_destroy(og);
   if (rc != LSLAM_OK) throw std::runtime_error(std::string("lslam_occgrid_read_u8: ") + lslam_last_error(ctx));
   karto::OccupancyGrid* grid = new karto::OccupancyGrid(dims[0], dims[1], karto::Vector2<kt_double>(off[0], off[1]), resolution);
   kt_int8u* data = grid->GetDataPointer();
   const size_t step = static_cast<size_t>(grid->GetWidthStep());
   for (int y = 0; y < dims[1]; y++) std::memcpy(data + y * step, &cells[static_cast<size_t>(y) * dims[0]], static_cast<size_t>(dims[0]));
+  if (ppDeviceGrid) *ppDeviceGrid = og;
   return grid;
+}
+
+inline karto::OccupancyGrid* CreateOccupancyGridFromScans(lslam_context* ctx, const karto::LocalizedRangeScanVector& rScans,
+                                                          kt_double resolution) {
+  return CreateOccupancyGridFromScans(ctx, rScans, resolution, NULL);
 }
 
 }  // namespace lslam
