@@ -477,7 +477,7 @@ __device__ __forceinline__ void first_valid_min(int* s_first, bool valid, int i)
   if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicMin(s_first, i);
 }
 
-constexpr int kRowsQueue = 256;  // >= 63 waiting + two blocks of 64 coming in
+constexpr int kRowsQueue = 256;  // >= 63 waiting + two blocks of 64 coming in (+ 64: an odd last block, see phase A)
 // LDS of ONE wave of the row kernel.  SOLO (k_resp_rows, a block = a wave): four arrays of their own.  In the scan-resident
 // step kernel (k_match_step: several waves per block, each on its own angle) a wave's area is 2.4 KB: `red` (epilogue) and
 // `queue` (phases A / B) are never live together and share their bytes, and the beams the fp32 estimate cannot decide are
@@ -893,10 +893,21 @@ __device__ __forceinline__ void resp_rows_wave(
         b0 += 2 * bstride;
         it += 2;
       };
+      // A scan of an odd number of blocks (1081 beams = 17) ends on a block without a partner: it goes in alone, behind
+      // both stages -- as the second of a pair, the empty block would still run its estimate, cell, occupancy word and
+      // ballot.  The stages below therefore take PAIRS only.
+      auto last_block_in = [&]() {
+        const int bA = b0 + lane;
+        bool validA;
+        int gxA, gyA;
+        estimate(it, pA_next, bA < g.n_beams, validA, gxA, gyA);
+        enqueue(std::false_type{}, bA, validA, true, gxA, gyA, 0, false, true, 0, 0);
+        b0 += 2 * bstride;
+      };
       // stage 1: nothing to drain yet -- the accumulators do not exist
       if constexpr (PEEL) {
-        while (b0 < g.n_beams && qcount < 64) two_blocks_in();
-        // the first drain writes them (a partial one when the scan ran out first; zeros when nothing is queued)
+        while (b0 + bstride < g.n_beams && qcount < 64) two_blocks_in();
+        // the first drain writes them (a partial one when the scan ran out of pairs first; zeros when nothing is queued)
         const int c = min(qcount, 64);
         if (c > 0) {
           drain_as(std::true_type{}, qhead, c);
@@ -915,10 +926,13 @@ __device__ __forceinline__ void resp_rows_wave(
         }
       }
       // stage 2: as before
-      while (b0 < g.n_beams) {
+      while (b0 + bstride < g.n_beams) {
         two_blocks_in();
         drain_ready(std::true_type{});
       }
+      // (not drained here -- one more inlined copy of phase B: up to 63 + 64 entries wait, the parked beams below add at
+      //  most 64 before their own drain, 191 <= kRowsQueue, and the drain that ends the pass takes them 64 at a time)
+      if (b0 < g.n_beams) last_block_in();
       if constexpr (SOLO) {
         for (int a0 = 0; a0 < acount; a0 += 64) {
           const bool valid = a0 + lane < acount;
@@ -961,7 +975,12 @@ __device__ __forceinline__ void resp_rows_wave(
         emit(std::false_type{}, b, valid, small, gx, gy, 0, false, true, 0, 0);
       }
     }
-    if (qcount > 0) drain(qhead, qcount);
+    while (qcount > 0) {
+      const int c = min(qcount, 64);
+      drain(qhead, c);
+      qhead = (qhead + c) & (kQueue - 1);
+      qcount -= c;
+    }
     wsync<SOLO>();
     LSLAM_PHASE_MARK(pck, 1);  // phases A + B: every beam's cell, the queued beams' rows
     if constexpr (STATS) {
