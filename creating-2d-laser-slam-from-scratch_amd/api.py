@@ -237,6 +237,70 @@ class Deskewer:
         return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
 
 
+FEATURE_SECTORS, FEATURE_PICKS, FEATURE_MAX_READINGS = 6, 20, 1500  # LSLAM_FEATURE_*
+FEATURE_RECORD = np.dtype([("n_valid", np.int32), ("n_corners", np.int32), ("per_sector", np.int32, (6,))])  # lslam_feature_record
+
+
+class FeatureExtractor:
+    """lslam_features: lesson1's LaserScan::ScanCallback (curvature corners: the 20 sharpest points of each sixth of a scan)
+    for many scans per launch.  Among equal curvatures the higher compacted index ranks first."""
+
+    def __init__(self, ctx: "Context", edge_threshold: float = 1.0):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_features_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        self.set_threshold(edge_threshold)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_features_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def set_threshold(self, edge_threshold: float):
+        self.ctx.check(self.L.lslam_features_set_threshold(self.h, float(edge_threshold)))
+
+    def extract(self, ranges, n_readings=None, want_image=True, want_curvature=True):
+        """ranges: [n_scans, stride] float32 (the first n_readings <= stride beams of each row are the scan) ->
+        (image [n_scans, n_readings] float32, index [n_scans, 6, 20] int32 of ORIGINAL beam indices (-1 = unused),
+        records FEATURE_RECORD[n_scans], curvature [n_scans, n_readings] float32); image / curvature are None when not
+        wanted."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        if r.ndim != 2:
+            raise ValueError("ranges must be [n_scans, stride]")
+        n, stride = r.shape
+        nr = stride if n_readings is None else int(n_readings)
+        image = np.zeros((n, max(nr, 0)), np.float32) if want_image else None
+        curv = np.zeros((n, max(nr, 0)), np.float32) if want_curvature else None
+        index = np.full((n, FEATURE_SECTORS, FEATURE_PICKS), -1, np.int32)
+        rec = np.zeros(n, FEATURE_RECORD)
+        self.ctx.check(self.L.lslam_features_batch(self.h, n, nr, r.ctypes.data, stride,
+                                                   image.ctypes.data if want_image else None, index.ctypes.data,
+                                                   rec.ctypes.data, curv.ctypes.data if want_curvature else None))
+        return image, index, rec, curv
+
+    def extract_dev(self, n_scans: int, n_readings: int, ranges_ptr: int, ranges_stride: int, image_ptr, index_ptr: int,
+                    records_ptr: int, curvature_ptr):
+        """The same with ranges and every output in HBM (image_ptr / curvature_ptr may be None): asynchronous on the
+        context's stream, no host wait."""
+        self.ctx.check(self.L.lslam_features_batch_dev(self.h, n_scans, n_readings, ranges_ptr, ranges_stride, image_ptr,
+                                                       index_ptr, records_ptr, curvature_ptr))
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_features_stats(self.h, out))
+        return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
 class GMapGeometry(C.Structure):
     _fields_ = [("map_size_x", C.c_int32), ("map_size_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("size_x2", C.c_int32), ("size_y2", C.c_int32), ("patches_x", C.c_int32), ("patches_y", C.c_int32),
@@ -440,6 +504,13 @@ def lib() -> C.CDLL:
     L.lslam_deskew_stats.argtypes = [vp, vp]
     L.lslam_deskew_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lslam_deskew_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_features_create.argtypes = [vp, C.POINTER(vp)]
+    L.lslam_features_destroy.argtypes = [vp]
+    L.lslam_features_destroy.restype = None
+    L.lslam_features_set_threshold.argtypes = [vp, C.c_float]
+    L.lslam_features_stats.argtypes = [vp, vp]
+    L.lslam_features_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.lslam_features_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.lslam_map_set_cloud.argtypes = [vp, vp, vp, i32, C.POINTER(HectorScan), C.POINTER(i32)]
     L.lslam_hector_process_many_deskewed.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp]

@@ -632,6 +632,63 @@ class LidarUndistortionGpu {
   lslam_deskew* h_ = nullptr;
 };
 
+// lesson1's LaserScan (lesson1/src/feature_detection.cc): ScanCallback's corner extraction, for one scan or many per
+// launch.  cornerRanges is what the node publishes as corner_scan.ranges (its first n entries): the range of every
+// picked beam, +0.0f elsewhere.  Among equal curvatures the higher compacted index ranks first (lslam_gpu.h).
+class LaserScanFeaturesGpu {
+ public:
+  explicit LaserScanFeaturesGpu(lslam_context* ctx, float edgeThreshold = 1.0f) : ctx_(ctx) {
+    check(lslam_features_create(ctx, &h_));
+    const int rc = lslam_features_set_threshold(h_, edgeThreshold);
+    if (rc != LSLAM_OK) {
+      lslam_features_destroy(h_);
+      check(rc);
+    }
+  }
+  ~LaserScanFeaturesGpu() { lslam_features_destroy(h_); }
+  LaserScanFeaturesGpu(const LaserScanFeaturesGpu&) = delete;
+  LaserScanFeaturesGpu& operator=(const LaserScanFeaturesGpu&) = delete;
+
+  // one scan of n beams; outIndex (120 original beam indices, -1 = unused slot) and outRecord may be NULL
+  void ScanCallback(const float* ranges, int n, float* cornerRanges, int32_t* outIndex = nullptr,
+                    lslam_feature_record* outRecord = nullptr) {
+    ScanCallbacks(1, n, ranges, n, cornerRanges, outIndex, outRecord);
+  }
+  // nScans scans of nReadings beams (row k at ranges + k * rangesStride).  cornerRanges: nScans x nReadings, outIndex:
+  // nScans x 120, outRecords: nScans; outIndex, outRecords and outCurvature (nScans x nReadings) may be NULL.
+  void ScanCallbacks(int nScans, int nReadings, const float* ranges, int rangesStride, float* cornerRanges,
+                     int32_t* outIndex = nullptr, lslam_feature_record* outRecords = nullptr, float* outCurvature = nullptr) {
+    if (nScans > 0 && !outIndex) {
+      index_.resize((size_t)nScans * LSLAM_FEATURE_SECTORS * LSLAM_FEATURE_PICKS);
+      outIndex = index_.data();
+    }
+    if (nScans > 0 && !outRecords) {
+      records_.resize((size_t)nScans);
+      outRecords = records_.data();
+    }
+    check(lslam_features_batch(h_, nScans, nReadings, ranges, rangesStride, cornerRanges, outIndex, outRecords, outCurvature));
+  }
+  // the same with ranges and every output in HBM (outIndexDev and outRecordsDev are required here): asynchronous on
+  // lslam_stream(ctx), no host wait
+  void ScanCallbacksDev(int nScans, int nReadings, const float* rangesDev, int rangesStride, float* cornerRangesDev,
+                        int32_t* outIndexDev, lslam_feature_record* outRecordsDev, float* outCurvatureDev = nullptr) {
+    check(lslam_features_batch_dev(h_, nScans, nReadings, rangesDev, rangesStride, cornerRangesDev, outIndexDev, outRecordsDev,
+                                   outCurvatureDev));
+  }
+  // {scans extracted, kernel launches, buffer growths, host waits}
+  void stats(int64_t out[4]) const { lslam_features_stats(h_, out); }
+  lslam_features* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_features* h_ = nullptr;
+  std::vector<int32_t> index_;
+  std::vector<lslam_feature_record> records_;
+};
+
 // gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's
 // ComputeMap (gmapping.cc:171-242).  cell() reads from a host copy of the counters, refreshed after every change.
 struct IntPoint2 {  // gmapping::IntPoint

@@ -978,6 +978,61 @@ int lslam_gmap_read_patch_mask(lslam_gmap* map, uint8_t* out);
 /* since the last reset: scans, beams used (past the range filter), hits applied, cell updates dropped outside */
 int lslam_gmap_stats(lslam_gmap* map, int64_t out[4]);
 
+/* ---------------------------------------------------------------------------------------- */
+/* lesson1 curvature corner extraction (LaserScan::ScanCallback, lesson1/src/                */
+/* feature_detection.cc:77-179): compact the finite ranges, an 11-point range curvature, the  */
+/* 20 sharpest points of each sixth of the scan.  Pinned BIT FOR BIT against the reference's  */
+/* own source (tests/golden/features_golden.npz, tests/test_features_gpu.py).                 */
+/*  1. Beams with a non-finite range (NaN, +-inf) are dropped; zero and negative ranges stay.  */
+/*     v[0..count) are the rest in order, map[i] their original beam index.                    */
+/*  2. For 5 <= i < count-5, in float32, left to right, every operation rounded:               */
+/*       d = v[i-5]+v[i-4]+v[i-3]+v[i-2]+v[i-1] - v[i]*10 + v[i+1]+v[i+2]+v[i+3]+v[i+4]+v[i+5] */
+/*       c[i] = d*d;  c = 0 at every other compacted index.                                    */
+/*  3. Sector j = 0..5 is [s, e] with s = count*j/6, e = count*(j+1)/6 - 1 (integers); a sector */
+/*     with s >= e is skipped whole.                                                           */
+/*  4. The reference sorts [s, e) -- without e -- and walks from e down: element e is picked   */
+/*     whenever c[e] > threshold, whatever its value, and uses one of the sector's 20 slots;   */
+/*     the other slots go to the largest c > threshold of [s, e), in descending order.         */
+/*  5. TIE RULE (this library's; the reference's order among equal curvatures is whatever its   */
+/*     unstable std::sort leaves): among equal curvatures the HIGHER compacted index ranks      */
+/*     first.  Where no equal curvatures straddle a sector's cut-off the picks are the          */
+/*     reference's; the number of picks per sector is the reference's everywhere.               */
+/* ---------------------------------------------------------------------------------------- */
+#define LSLAM_FEATURE_SECTORS 6
+#define LSLAM_FEATURE_PICKS 20          /* per sector */
+#define LSLAM_FEATURE_MAX_READINGS 1500 /* max_scan_count, feature_detection.cc:23 */
+typedef struct lslam_feature_record {
+  int32_t n_valid;       /* count: the finite beams */
+  int32_t n_corners;     /* the sum of per_sector */
+  int32_t per_sector[6]; /* picks of each sector, 0..20 */
+} lslam_feature_record;  /* 32 bytes */
+typedef struct lslam_features lslam_features;
+int lslam_features_create(lslam_context* ctx, lslam_features** out);
+void lslam_features_destroy(lslam_features* f);
+/* edge_threshold_ (:69), 1.0f by default.  NaN or below 0 -> LSLAM_ERR_INVALID_ARGUMENT (there the reference would pick
+ * its value-initialised entries). */
+int lslam_features_set_threshold(lslam_features* f, float edge_threshold);
+/* n_scans scans of n_readings beams in ONE launch (a workgroup per scan, everything per scan in LDS); row k of ranges at
+ * ranges + k * ranges_stride -- the block layout lslam_matcher_match_batch_dev_f32 and lslam_deskew_batch_dev take.
+ *  out_ranges    n_scans x n_readings float32, may be NULL: the reference's published corner_scan.ranges (its first
+ *                n_readings entries): the range of every pick at its beam, +0.0f elsewhere
+ *  out_index     n_scans x 120 int32: ORIGINAL beam indices; sector j owns slots [20j, 20j+20): element e first if it was
+ *                picked, then descending curvature (ties by the rule above); unused slots are -1
+ *  out_rec       n_scans records
+ *  out_curvature n_scans x n_readings float32, may be NULL: c scattered to the original beam index, 0 elsewhere
+ * n_scans == 0 is LSLAM_OK and launches nothing; n_readings == 0 is LSLAM_OK and leaves every scan empty (all slots -1, a
+ * zero record).  At most 65535 scans per call and LSLAM_FEATURE_MAX_READINGS beams per scan (LSLAM_ERR_UNSUPPORTED beyond:
+ * the reference's stack arrays end there).  The handle owns every buffer the host form needs: a repeated shape allocates
+ * nothing, and the call waits once, at its end.  The _dev form takes ranges and every out_* in HBM, is ASYNCHRONOUS on
+ * lslam_stream() and makes no host wait; every scan of a batch is bit for bit the same scan run alone. */
+int lslam_features_batch(lslam_features* f, int n_scans, int n_readings, const float* ranges, int ranges_stride,
+                         float* out_ranges, int32_t* out_index, lslam_feature_record* out_rec, float* out_curvature);
+int lslam_features_batch_dev(lslam_features* f, int n_scans, int n_readings, const float* ranges_dev, int ranges_stride,
+                             float* out_ranges_dev, int32_t* out_index_dev, lslam_feature_record* out_rec_dev,
+                             float* out_curvature_dev);
+/* out = {scans extracted, kernel launches, buffer growths (device or pinned), host waits} */
+int lslam_features_stats(const lslam_features* f, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
