@@ -448,7 +448,9 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // v_perm_b32 into FOUR candidates per dword in packed 16-bit fields.
 // Epilogue: three packed DPP adds reduce over groups of 8 lanes, 2 KB of LDS brings the 8 partials of
 // each packed word to one lane, which writes exact int32 sums angle-major (coalesced).
-// No MFMA: this is a gather/compare path over an L2-resident 4 MB grid.
+// MFMA = true (the default form, LSLAM_OPT_ROWS_MFMA): phase B realigns the row with v_alignbyte_b32 and sums the bytes of the
+// 64 queued beams with v_mfma_i32_16x16x64_i8 against a one-hot operand, the epilogue is a few adds and two row swaps -- see
+// resp_rows_wave.  The gathers over the L2-resident 4 MB grid are the same in both forms.
 // Block -> (scan, angle) mapping keeps all angles of a scan on one XCD (block b runs on XCD b%8),
 // so a scan's 17 KB of scan-frame points is fetched into ONE L2 instead of eight.
 // ------------------------------------------------------------------------------------------
@@ -503,7 +505,15 @@ __device__ __forceinline__ void wsync() {
 
 // One wave64: all nX*nY numerators of (scan s, angle a[, beam slice]).  SOLO: written to resp (global, angle-major; beam
 // slices accumulate with atomics); !SOLO: stored to lds_out[a * ncand + ...] (the block's numerators live in LDS).
-template <int NXD, int NYC, bool TILED, bool STATS, bool LDSB, bool SOLO, bool OUT_LDS = !SOLO>
+// MFMA = true (LSLAM_OPT_ROWS_MFMA): phase B sums the queued rows' bytes on the matrix pipe.  The lane's 16 realigned
+// candidate bytes are the A operand of v_mfma_i32_16x16x64_i8 and B is a per-lane one-hot (byte lane & 15 = 1): the
+// instruction pairs element j of A's lane group with element j of B's, and every lane group holds the same one-hot, so
+//     D[m][n] = sum over the lanes m, m + 16, m + 32, m + 48 of their byte n
+// whatever the hardware's k numbering.  One int32x4 accumulator per lattice row (lane l holds D[4 (l >> 4) + 0..3][l & 15]);
+// the epilogue adds its four registers and the four 16-lane rows, and lane n < nx stores candidate n.  The bytes are read as
+// SIGNED: the host takes this form only for grids whose bytes are all <= 127 (every grid the library builds is <= 100).
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+template <int NXD, int NYC, bool TILED, bool STATS, bool LDSB, bool SOLO, bool OUT_LDS = !SOLO, bool MFMA = false>
 __device__ __forceinline__ void resp_rows_wave(
     const int s, const int a, const int slice, const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int step,
     int limit, const Geom& g, const PassCfg& pc, const Lattice* __restrict__ lat, const double2* __restrict__ cossin,
@@ -516,6 +526,7 @@ __device__ __forceinline__ void resp_rows_wave(
   static_assert(NYC <= 16 && 2 * (NYC - 1) < 32, "row mask / occupancy window width");
   static_assert(SOLO || (!STATS && !LDSB), "multi-wave blocks run the production variants only");
   static_assert(!(SOLO && OUT_LDS), "a lone wave writes its numerators to global memory");
+  static_assert(!MFMA || (!LDSB && NXD >= 3 && NXD <= 4), "the MFMA accumulate takes rows of 9..16 candidates from global memory");
   uint32_t (*const red)[8] = lds.red;
   int2* const queue = lds.queue;
   [[maybe_unused]] uint16_t* const ambq = lds.ambq;
@@ -554,8 +565,12 @@ __device__ __forceinline__ void resp_rows_wave(
 #else
     constexpr bool PEEL = EST;
 #endif
-    uint32_t acc[NYC][NXD][2];
-    if constexpr (!PEEL) {
+    [[maybe_unused]] uint32_t acc[MFMA ? 1 : NYC][NXD][2];
+    [[maybe_unused]] v4i_t macc[MFMA ? NYC : 1];  // MFMA: D of lattice row j, summed over the drains in int32
+    if constexpr (MFMA && !PEEL) {
+#pragma unroll
+      for (int j = 0; j < NYC; j++) macc[j] = v4i_t{0, 0, 0, 0};
+    } else if constexpr (!PEEL) {
 #pragma unroll
       for (int j = 0; j < NYC; j++)
 #pragma unroll
@@ -579,8 +594,8 @@ __device__ __forceinline__ void resp_rows_wave(
       const uint32_t sh = (uint32_t)e.x & 3u;
       // v_perm_b32 selectors: bytes sh+0 / sh+2 (even candidates) and sh+1 / sh+3 (odd) of the word pair,
       // each zero-extended into a 16-bit field (0x0C selects the constant 0)
-      const uint32_t sel_e = 0x0C020C00u + sh * 0x00010001u;
-      const uint32_t sel_o = 0x0C030C01u + sh * 0x00010001u;
+      [[maybe_unused]] const uint32_t sel_e = 0x0C020C00u + sh * 0x00010001u;
+      [[maybe_unused]] const uint32_t sel_o = 0x0C030C01u + sh * 0x00010001u;
       uint32_t wv[NYC][NXD + 1];
       if constexpr (TILED) {
         // e.x = X' | parity << 15 | (y + kTileYOff) << 16 (k_tile_planes): lattice row j is class row
@@ -658,20 +673,38 @@ __device__ __forceinline__ void resp_rows_wave(
           }
         }
       }
+      if constexpr (MFMA) {
+        // B: one-hot over the lane's 16 bytes (byte lane & 15); A: the row's bytes sh .. sh + 15, candidate n in byte n
+        // (<3,11>: the last word is not realigned -- bytes 12..15 are candidates no lattice of this form has)
+        const uint32_t hot = 1u << ((lane & 3) * 8), hq = ((uint32_t)lane >> 2) & 3u;
+        const v4i_t B{(int)(hq == 0u ? hot : 0u), (int)(hq == 1u ? hot : 0u), (int)(hq == 2u ? hot : 0u), (int)(hq == 3u ? hot : 0u)};
 #pragma unroll
-      for (int j = 0; j < NYC; j++)
+        for (int j = 0; j < NYC; j++) {
+          v4i_t A;
 #pragma unroll
-        for (int k = 0; k < NXD; k++) {
-          const uint32_t pe = __builtin_amdgcn_perm(wv[j][k + 1], wv[j][k], sel_e);  // candidates 4k, 4k+2
-          const uint32_t po = __builtin_amdgcn_perm(wv[j][k + 1], wv[j][k], sel_o);  // candidates 4k+1, 4k+3
-          if constexpr (FIRST) {
-            acc[j][k][0] = pe;
-            acc[j][k][1] = po;
-          } else {
-            acc[j][k][0] += pe;
-            acc[j][k][1] += po;
-          }
+          for (int k = 0; k < 4; k++)
+            A[k] = k < NXD ? (int)__builtin_amdgcn_alignbyte(wv[j][k + 1], wv[j][k], sh) : (int)wv[j][k];
+          if constexpr (FIRST)
+            macc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, v4i_t{0, 0, 0, 0}, 0, 0, 0);
+          else
+            macc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, macc[j], 0, 0, 0);
         }
+      } else {
+#pragma unroll
+        for (int j = 0; j < NYC; j++)
+#pragma unroll
+          for (int k = 0; k < NXD; k++) {
+            const uint32_t pe = __builtin_amdgcn_perm(wv[j][k + 1], wv[j][k], sel_e);  // candidates 4k, 4k+2
+            const uint32_t po = __builtin_amdgcn_perm(wv[j][k + 1], wv[j][k], sel_o);  // candidates 4k+1, 4k+3
+            if constexpr (FIRST) {
+              acc[j][k][0] = pe;
+              acc[j][k][1] = po;
+            } else {
+              acc[j][k][0] += pe;
+              acc[j][k][1] += po;
+            }
+          }
+      }
     };
     auto drain = [&](int head, int cnt) { drain_as(std::false_type{}, head, cnt); };
 
@@ -913,6 +946,9 @@ __device__ __forceinline__ void resp_rows_wave(
           drain_as(std::true_type{}, qhead, c);
           qhead = (qhead + c) & (kQueue - 1);
           qcount -= c;
+        } else if constexpr (MFMA) {
+#pragma unroll
+          for (int j = 0; j < NYC; j++) macc[j] = v4i_t{0, 0, 0, 0};
         } else {
 #pragma unroll
           for (int j = 0; j < NYC; j++)
@@ -993,72 +1029,95 @@ __device__ __forceinline__ void resp_rows_wave(
       }
     }
 
-    // Reduce over the wave.  A lane saw at most kMaxBeamsPerLane beams (the host slices longer scans),
-    // so three packed DPP adds -- lanes xor 1, xor 2, then the mirrored quad -- leave every group of 8
-    // lanes holding its 16-bit field sums without overflow; the 8 group partials of each packed word
-    // go through 2 KB of LDS to one lane, which unpacks them into exact int32 sums.
+    if constexpr (MFMA) {
+      // Reduce over the wave: the accumulator's four registers in the lane (rows 4 (l >> 4) + 0..3 of D), then the four
+      // 16-lane rows with the two row swaps (v_permlane32_swap, v_permlane16_swap: x[l] + x[l ^ 32], then + x[l ^ 16]);
+      // every lane then holds candidate l & 15 of lattice row j, and lanes 0 .. nx - 1 store it.  No LDS.
 #pragma unroll
-    for (int j = 0; j < NYC; j++)
-#pragma unroll
-      for (int k = 0; k < NXD; k++)
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          uint32_t v = acc[j][k][q];
-          v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
-          v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-          // row_half_mirror; written as the fused DPP add the compiler emits for the two steps above but not for this one
-          // (it used v_mov_b32_dpp + v_add_u32: one VALU instruction more per accumulator, 66 per wave)
-#if defined(LSLAM_EXP_NO_FUSED_DPP)  // A/B switch: round 4's form
-          v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);
-#else
-          asm("s_nop 1\n\tv_add_u32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(v));
-#endif
-          if ((lane & 7) == 0) red[(j * NXD + k) * 2 + q][lane >> 3] = v;
-        }
-    wsync<SOLO>();
-    for (int idx = lane; idx < NW; idx += 64) {
-      uint32_t lo = 0, hi = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const uint32_t v = red[idx][k];
-        lo += v & 0xFFFFu;
-        hi += v >> 16;
-      }
-      const int par2 = idx & 1, jk = idx >> 1;
-      const int j = j0 + jk / NXD, i = 4 * (jk % NXD) + par2;
-      if (j < pc.ny) {
-        if constexpr (OUT_LDS) {
-          int32_t* o = lds_out + a * ncand + j * pc.nx + i;
-          if (i < pc.nx) o[0] = (int32_t)lo;
-          if (i + 2 < pc.nx) o[2] = (int32_t)hi;
-        } else {
-          int32_t* o = resp + (size_t)s * resp_stride + (size_t)a * ncand + (size_t)j * pc.nx + i;
-          if (beam_slices == 1) {
-            if (i < pc.nx) o[0] = (int32_t)lo;
-            if (i + 2 < pc.nx) o[2] = (int32_t)hi;
+      for (int j = 0; j < NYC; j++) {
+        uint32_t v = (uint32_t)((macc[j][0] + macc[j][1]) + (macc[j][2] + macc[j][3]));
+        const auto h = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        v = h[0] + h[1];
+        const auto q = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+        v = q[0] + q[1];
+        if (lane < pc.nx && j0 + j < pc.ny) {
+          if constexpr (OUT_LDS) {
+            lds_out[a * ncand + (j0 + j) * pc.nx + lane] = (int32_t)v;
           } else {
-            if (i < pc.nx) atomicAdd(o, (int32_t)lo);
-            if (i + 2 < pc.nx) atomicAdd(o + 2, (int32_t)hi);
+            int32_t* o = resp + (size_t)s * resp_stride + (size_t)a * ncand + (size_t)(j0 + j) * pc.nx + lane;
+            if (beam_slices == 1) *o = (int32_t)v;
+            else atomicAdd(o, (int32_t)v);
           }
         }
       }
+    } else {
+      // Reduce over the wave.  A lane saw at most kMaxBeamsPerLane beams (the host slices longer scans),
+      // so three packed DPP adds -- lanes xor 1, xor 2, then the mirrored quad -- leave every group of 8
+      // lanes holding its 16-bit field sums without overflow; the 8 group partials of each packed word
+      // go through 2 KB of LDS to one lane, which unpacks them into exact int32 sums.
+#pragma unroll
+      for (int j = 0; j < NYC; j++)
+#pragma unroll
+        for (int k = 0; k < NXD; k++)
+#pragma unroll
+          for (int q = 0; q < 2; q++) {
+            uint32_t v = acc[j][k][q];
+            v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+            v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+            // row_half_mirror; written as the fused DPP add the compiler emits for the two steps above but not for this one
+            // (it used v_mov_b32_dpp + v_add_u32: one VALU instruction more per accumulator, 66 per wave)
+#if defined(LSLAM_EXP_NO_FUSED_DPP)  // A/B switch: round 4's form
+            v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);
+#else
+            asm("s_nop 1\n\tv_add_u32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(v));
+#endif
+            if ((lane & 7) == 0) red[(j * NXD + k) * 2 + q][lane >> 3] = v;
+          }
+      wsync<SOLO>();
+      for (int idx = lane; idx < NW; idx += 64) {
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const uint32_t v = red[idx][k];
+          lo += v & 0xFFFFu;
+          hi += v >> 16;
+        }
+        const int par2 = idx & 1, jk = idx >> 1;
+        const int j = j0 + jk / NXD, i = 4 * (jk % NXD) + par2;
+        if (j < pc.ny) {
+          if constexpr (OUT_LDS) {
+            int32_t* o = lds_out + a * ncand + j * pc.nx + i;
+            if (i < pc.nx) o[0] = (int32_t)lo;
+            if (i + 2 < pc.nx) o[2] = (int32_t)hi;
+          } else {
+            int32_t* o = resp + (size_t)s * resp_stride + (size_t)a * ncand + (size_t)j * pc.nx + i;
+            if (beam_slices == 1) {
+              if (i < pc.nx) o[0] = (int32_t)lo;
+              if (i + 2 < pc.nx) o[2] = (int32_t)hi;
+            } else {
+              if (i < pc.nx) atomicAdd(o, (int32_t)lo);
+              if (i + 2 < pc.nx) atomicAdd(o + 2, (int32_t)hi);
+            }
+          }
+        }
+      }
+      wsync<SOLO>();
     }
-    wsync<SOLO>();
     LSLAM_PHASE_MARK(pck, 2);  // wave reduction + stores
   }
   if constexpr (SOLO) LSLAM_PHASE_FLUSH(pck, g_sm_stamps, 5, (unsigned)blockIdx.x, (threadIdx.x & 63) == 0);
 }
 
 // The row kernel proper: one wave64 per block.
-template <int NXD, int NYC, bool TILED, bool STATS = false, bool LDSB = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))  // <= 128 VGPRs
+template <int NXD, int NYC, bool TILED, bool MFMA = false, bool STATS = false, bool LDSB = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))  // <= 128 VGPRs (AGPRs included)
 k_resp_rows(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int step, int limit, Geom g,
             PassCfg pc, const Lattice* __restrict__ lat, const double2* __restrict__ cossin,
             const double2* __restrict__ local, int32_t* __restrict__ resp, size_t resp_stride, int beam_slices,
             int S, const uint2* __restrict__ occ_t, int occ_wpc, int tile_rows, uint32_t tile_class_bytes,
             unsigned long long* __restrict__ stats) {
   constexpr int NW = NXD * NYC * 2;
-  __shared__ __align__(16) uint32_t red[NW][8];
+  __shared__ __align__(16) uint32_t red[MFMA ? 1 : NW][8];  // (the MFMA form's epilogue does not go through LDS)
   __shared__ int2 queue[kRowsQueue];
   __shared__ uint16_t ambq[TILED ? 64 * kMaxBeamsPerLane : 1];
   __shared__ uint32_t patch[LDSB ? 2 : 1][LDSB ? kPatchDw : 1];
@@ -1069,10 +1128,9 @@ k_resp_rows(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, 
   const int s = (r / pc.na) * 8 + xcd;
   const int a = r % pc.na;
   if (s >= S) return;
-  resp_rows_wave<NXD, NYC, TILED, STATS, LDSB, true>(s, a, slice, src0, src1, step, limit, g, pc, lat, cossin, local, resp,
-                                                     resp_stride, beam_slices, occ_t, occ_wpc, tile_rows, tile_class_bytes,
-                                                     stats, RowsLds{red, queue, ambq, (uint32_t (*)[kPatchDw])patch, nullptr},
-                                                     nullptr);
+  resp_rows_wave<NXD, NYC, TILED, STATS, LDSB, true, false, MFMA>(
+      s, a, slice, src0, src1, step, limit, g, pc, lat, cossin, local, resp, resp_stride, beam_slices, occ_t, occ_wpc, tile_rows,
+      tile_class_bytes, stats, RowsLds{red, queue, ambq, (uint32_t (*)[kPatchDw])patch, nullptr}, nullptr);
 }
 
 // The same waves in blocks of WAVES: the waves of a block take WAVES consecutive angles of ONE scan, so they run on ONE CU
@@ -1087,7 +1145,7 @@ constexpr int rows_wave_area() {  // bytes of LDS per wave: max(red, queue) + th
              ? (NXD == 3 ? 3 * 11 * 2 * 8 * 4 : 4 * 8 * 2 * 8 * 4) + kMaxBeamsPerLane * 8
              : kRowsQueue * 8 + kMaxBeamsPerLane * 8;
 }
-template <int NXD, int NYC, int WAVES>
+template <int NXD, int NYC, int WAVES, bool MFMA = false>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8)))
 k_resp_rows_mw(const uint8_t* __restrict__ ptiles, int limit, Geom g, PassCfg pc, const Lattice* __restrict__ lat,
                const double2* __restrict__ cossin, const double2* __restrict__ local, int32_t* __restrict__ resp,
@@ -1104,9 +1162,10 @@ k_resp_rows_mw(const uint8_t* __restrict__ ptiles, int limit, Geom g, PassCfg pc
   if (s >= S || a >= pc.na) return;
   unsigned char* wa = areas + wave * kArea;
   const RowsLds lds{(uint32_t (*)[8])wa, (int2*)wa, nullptr, nullptr, (unsigned long long*)(wa + (kArea - kMaxBeamsPerLane * 8))};
-  resp_rows_wave<NXD, NYC, true, false, false, false, false>(s, a, 0, ptiles, ptiles, 2, limit, g, pc, lat, cossin, local, resp,
-                                                             resp_stride, 1, occ_t, occ_wpc, tile_rows, tile_class_bytes,
-                                                             (unsigned long long*)nullptr, lds, (int32_t*)nullptr);
+  resp_rows_wave<NXD, NYC, true, false, false, false, false, MFMA>(s, a, 0, ptiles, ptiles, 2, limit, g, pc, lat, cossin, local,
+                                                                   resp, resp_stride, 1, occ_t, occ_wpc, tile_rows,
+                                                                   tile_class_bytes, (unsigned long long*)nullptr, lds,
+                                                                   (int32_t*)nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3635,6 +3694,11 @@ struct lslam_matcher {
   bool collect_stats = false;       // lslam_matcher_set_option(LSLAM_OPT_COLLECT_STATS): instrumented coarse kernel
   bool lds_staged = false;          // lslam_matcher_set_option(LSLAM_OPT_LDS_STAGED): the measured-and-dropped LDS-staged phase B
   int rows_waves = 1;               // lslam_matcher_set_option(LSLAM_OPT_ROWS_WAVES): waves per block of the tiled coarse kernel (1 = k_resp_rows, 2 / 4 / 8 = k_resp_rows_mw)
+  bool rows_mfma = true;            // lslam_matcher_set_option(LSLAM_OPT_ROWS_MFMA): phase B of k_resp_rows / k_resp_rows_mw sums on the matrix pipe
+  // the grid's bytes are all <= 127 (the i8 MFMA reads them signed): true for every grid the library builds (<= kOccupied),
+  // checked on the host copy by lslam_matcher_set_grid_u8, false after lslam_matcher_set_grid_u8_dev (bytes unseen)
+  bool grid_fits_i8 = true;
+  int64_t rows_mfma_launches = 0;   // coarse / fine row launches that took the MFMA accumulate (lslam_matcher_rows_mfma_launches)
   // the streaming front-end's speculative anchor chain (anchor_spec_block): asked for before a match, reported after it
   SpecArgs spec_req{};
   bool spec_armed = false, spec_launched = false;
@@ -4040,6 +4104,13 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
       (const double2*)m->d_local.p, m->d_resp.p, resp_stride, slices, S, occ, m->occ_wpc, m->ptile_rows, class_bytes, \
       (unsigned long long*)(m->collect_stats ? m->d_stats.p : nullptr)
       const uint8_t* pt = m->d_ptiles;
+      // the MFMA accumulate (LSLAM_OPT_ROWS_MFMA) reads the grid's bytes signed: a grid with a byte above 127 keeps the packed form
+      bool mfma = m->rows_mfma && m->grid_fits_i8;
+#define LSLAM_ROWS(NXD_, NYC_, TILED_, STATS_, SRC0, SRC1)                                           \
+  do {                                                                                               \
+    if (mfma) launch(ctx, name, k_resp_rows<NXD_, NYC_, TILED_, true, STATS_>, LSLAM_ROWS_ARGS(SRC0, SRC1)); \
+    else launch(ctx, name, k_resp_rows<NXD_, NYC_, TILED_, false, STATS_>, LSLAM_ROWS_ARGS(SRC0, SRC1));     \
+  } while (0)
       if (m->collect_stats && (variant == 2 || variant == 3) && step == 2 && m->stats_scans < S) {
         // (re)size the per-(scan, beam) flag words behind the counters; the counters collected so far are carried over
         unsigned long long keep[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -4056,33 +4127,35 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
       int form;  // which of the forms below takes this pass (host-side count: lslam_matcher_coarse_form_launches)
       if (m->lds_staged && variant == 2 && step == 2) {  // experiment (DESIGN_HISTORY.md B): phase B through LDS patches
         form = m->collect_stats ? LSLAM_FORM_ROWS_STATS_LDS_STAGED : LSLAM_FORM_ROWS_LDS_STAGED;
+        mfma = false;  // the experiment stays on the packed sums
         if (m->collect_stats)
-          launch(ctx, name, k_resp_rows<3, 11, false, true, true>, LSLAM_ROWS_ARGS(s0, s1));
+          launch(ctx, name, k_resp_rows<3, 11, false, false, true, true>, LSLAM_ROWS_ARGS(s0, s1));
         else
-          launch(ctx, name, k_resp_rows<3, 11, false, false, true>, LSLAM_ROWS_ARGS(s0, s1));
+          launch(ctx, name, k_resp_rows<3, 11, false, false, false, true>, LSLAM_ROWS_ARGS(s0, s1));
       } else if (m->collect_stats && variant == 2 && step == 2) {  // instrumented twin (untimed diagnostics only)
         form = ptiled ? LSLAM_FORM_ROWS_STATS_TILED : LSLAM_FORM_ROWS_STATS_LINEAR;
-        if (ptiled)
-          launch(ctx, name, k_resp_rows<3, 11, true, true>, LSLAM_ROWS_ARGS(pt, pt));
-        else
-          launch(ctx, name, k_resp_rows<3, 11, false, true>, LSLAM_ROWS_ARGS(s0, s1));
+        if (ptiled) LSLAM_ROWS(3, 11, true, true, pt, pt);
+        else LSLAM_ROWS(3, 11, false, true, s0, s1);
       } else if (m->collect_stats && variant == 3 && step == 2) {  // the same for lattice rows of 13..16 positions
         form = ptiled ? LSLAM_FORM_ROWS_STATS_TILED : LSLAM_FORM_ROWS_STATS_LINEAR;
-        if (ptiled)
-          launch(ctx, name, k_resp_rows<4, 8, true, true>, LSLAM_ROWS_ARGS(pt, pt));
-        else
-          launch(ctx, name, k_resp_rows<4, 8, false, true>, LSLAM_ROWS_ARGS(s0, s1));
+        if (ptiled) LSLAM_ROWS(4, 8, true, true, pt, pt);
+        else LSLAM_ROWS(4, 8, false, true, s0, s1);
       } else if (variant == 1) {
         form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
+        mfma = false;  // rows of up to 4 candidates: a quarter of an MFMA's columns, and not where the time goes
         launch(ctx, name, k_resp_rows<1, 4, false>, LSLAM_ROWS_ARGS(s0, s1));
       } else if ((variant == 2 || variant == 3) && ptiled && m->rows_waves > 1 && g.n_beams <= 64 * kMaxBeamsPerLane) {
         form = LSLAM_FORM_ROWS_MULTIWAVE;
         const int W = m->rows_waves, groups = (p.na + W - 1) / W;
         const dim3 mw_grid((unsigned)((long long)((S + 7) / 8) * 8 * groups));
-#define LSLAM_MW(NXD_, NYC_, W_)                                                                                         \
-  launch(ctx, name, k_resp_rows_mw<NXD_, NYC_, W_>, mw_grid, dim3(64 * W_), 0, pt, limit, g, p, (const Lattice*)m->d_lat.p, \
-         (const double2*)m->d_cossin.p, (const double2*)m->d_local.p, m->d_resp.p, resp_stride, S, occ, m->occ_wpc,      \
-         m->ptile_rows, class_bytes)
+#define LSLAM_MW_ARGS(W_)                                                                                         \
+  mw_grid, dim3(64 * W_), 0, pt, limit, g, p, (const Lattice*)m->d_lat.p, (const double2*)m->d_cossin.p,          \
+      (const double2*)m->d_local.p, m->d_resp.p, resp_stride, S, occ, m->occ_wpc, m->ptile_rows, class_bytes
+#define LSLAM_MW(NXD_, NYC_, W_)                                                                   \
+  do {                                                                                             \
+    if (mfma) launch(ctx, name, k_resp_rows_mw<NXD_, NYC_, W_, true>, LSLAM_MW_ARGS(W_));          \
+    else launch(ctx, name, k_resp_rows_mw<NXD_, NYC_, W_, false>, LSLAM_MW_ARGS(W_));              \
+  } while (0)
         if (variant == 2 && W == 2) LSLAM_MW(3, 11, 2);
         else if (variant == 2 && W == 4) LSLAM_MW(3, 11, 4);
         else if (variant == 2 && W == 8) LSLAM_MW(3, 11, 8);
@@ -4090,20 +4163,23 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
         else if (variant == 3 && W == 4) LSLAM_MW(4, 8, 4);
         else LSLAM_MW(4, 8, 8);
 #undef LSLAM_MW
+#undef LSLAM_MW_ARGS
       } else if (variant == 2 && ptiled) {
         form = LSLAM_FORM_ROWS_TILED;
-        launch(ctx, name, k_resp_rows<3, 11, true>, LSLAM_ROWS_ARGS(pt, pt));
+        LSLAM_ROWS(3, 11, true, false, pt, pt);
       } else if (variant == 2) {
         form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
-        launch(ctx, name, k_resp_rows<3, 11, false>, LSLAM_ROWS_ARGS(s0, s1));
+        LSLAM_ROWS(3, 11, false, false, s0, s1);
       } else if (ptiled) {
         form = LSLAM_FORM_ROWS_TILED;
-        launch(ctx, name, k_resp_rows<4, 8, true>, LSLAM_ROWS_ARGS(pt, pt));
+        LSLAM_ROWS(4, 8, true, false, pt, pt);
       } else {
         form = step == 1 ? LSLAM_FORM_FINE_ROWS : LSLAM_FORM_ROWS_LINEAR;
-        launch(ctx, name, k_resp_rows<4, 8, false>, LSLAM_ROWS_ARGS(s0, s1));
+        LSLAM_ROWS(4, 8, false, false, s0, s1);
       }
       m->form_launches[form]++;
+      if (mfma) m->rows_mfma_launches++;
+#undef LSLAM_ROWS
 #undef LSLAM_ROWS_ARGS
     } else {
       m->form_launches[LSLAM_FORM_GENERIC]++;
@@ -4532,6 +4608,7 @@ int rebuild_grid_dev(lslam_matcher* m, const double2* d_world, int ring_start, i
   }
   m->resp_prezeroed = x.zero == m->d_resp.p && x.zero ? (size_t)x.zero_words : 0;
   m->sub_dirty = m->occ_dirty = m->tile_dirty = m->ptile_dirty = true;
+  m->grid_fits_i8 = true;  // a rebuilt grid holds smear-kernel values: kround(z * kOccupied) <= kOccupied
   if (B <= 0 || n <= 0) return LSLAM_OK;
   LSLAM_HIP(ctx, m->d_valid.reserve((size_t)B * n));
   if (!use_lds) LSLAM_HIP(ctx, m->d_fv_scratch.reserve((size_t)B * 2 * n));
@@ -4840,6 +4917,11 @@ int lslam_matcher_set_grid_u8(lslam_matcher* m, const uint8_t* grid, const doubl
   m->g.off_x = offset_xy[0];
   m->g.off_y = offset_xy[1];
   m->sub_dirty = m->occ_dirty = m->tile_dirty = m->ptile_dirty = true;
+  {  // LSLAM_OPT_ROWS_MFMA reads the bytes signed: scan the host copy once, here
+    bool fits = true;
+    for (size_t i = 0, n = (size_t)m->g.data_size; i < n && fits; i++) fits = grid[i] < 128;
+    m->grid_fits_i8 = fits;
+  }
   return LSLAM_OK;
 }
 
@@ -4855,6 +4937,7 @@ int lslam_matcher_set_grid_u8_dev(lslam_matcher* m, const uint8_t* grid_dev, con
   m->g.off_x = offset_xy[0];
   m->g.off_y = offset_xy[1];
   m->sub_dirty = m->occ_dirty = m->tile_dirty = m->ptile_dirty = true;
+  m->grid_fits_i8 = false;  // bytes the host has not seen: not eligible for LSLAM_OPT_ROWS_MFMA (no per-step check, no sync)
   return LSLAM_OK;
 }
 
@@ -4912,6 +4995,9 @@ int lslam_matcher_set_option(lslam_matcher* m, int option, int value) {
       m->rows_waves = value;
       return LSLAM_OK;
     }
+    case LSLAM_OPT_ROWS_MFMA:
+      m->rows_mfma = value != 0;
+      return LSLAM_OK;
     case LSLAM_OPT_STEP_MIN_SCANS: {
       if (value < 1) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "step kernel: minimum batch %d < 1", value);
       m->step_min_scans = value;
@@ -4941,6 +5027,7 @@ int lslam_matcher_get_option(const lslam_matcher* m, int option) {
     case LSLAM_OPT_STEP_KERNEL: return m->step_waves;
     case LSLAM_OPT_STEP_MIN_SCANS: return m->step_min_scans;
     case LSLAM_OPT_ROWS_WAVES: return m->rows_waves;
+    case LSLAM_OPT_ROWS_MFMA: return m->rows_mfma ? 1 : 0;
     case LSLAM_OPT_CHECK_OUTPUT_REUSE: return m->check_out_reuse ? 1 : 0;
     case LSLAM_OPT_LONE_KERNEL: return m->lone_waves + (m->lone_waves && m->lone_one_task_wave ? 100 : 0);
     default: return LSLAM_ERR_INVALID_ARGUMENT;
@@ -4956,6 +5043,7 @@ int lslam_matcher_flush(lslam_matcher* m) {
 int64_t lslam_matcher_pipelined_steps(const lslam_matcher* m) { return m ? (int64_t)m->pipe_steps : 0; }
 int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->step_launches : 0; }
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->lone_launches : 0; }
+int64_t lslam_matcher_rows_mfma_launches(const lslam_matcher* m) { return m ? m->rows_mfma_launches : 0; }
 int lslam_matcher_coarse_form_launches(const lslam_matcher* m, int64_t out[LSLAM_FORM_COUNT]) {
   if (!m || !out) return LSLAM_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < LSLAM_FORM_COUNT; i++) out[i] = m->form_launches[i];

@@ -201,8 +201,18 @@ void* lslam_matcher_grid_dev_ptr(lslam_matcher* m);
  *    than the four launches (profiles/r06/experiments/README.md section 6), hence off by default; value + 100 = one task wave
  *    per block (the A/B form).  lslam_matcher_lone_kernel_launches counts the matches that did go out as one kernel.  The
  *    reference has no counterpart. */
+/*  LSLAM_OPT_ROWS_MFMA (default 1): the coarse response kernel (k_resp_rows / k_resp_rows_mw, lattice rows of 5..16
+ *    positions, the instrumented twins included) sums the bytes of its queued rows with v_mfma_i32_16x16x64_i8 -- the
+ *    lane's 16 candidate bytes against a one-hot operand, int32 accumulators -- instead of packed 16-bit fields on the
+ *    VALU.  The instruction reads the bytes SIGNED, so the form is taken only while every byte of the grid is <= 127:
+ *    always for a grid the library builds (<= 100), after lslam_matcher_set_grid_u8 if its host copy says so, never after
+ *    lslam_matcher_set_grid_u8_dev (bytes the host has not seen); any other grid, and value 0, runs the packed form.  Same
+ *    numerators either way; the launches are counted under the same form names, and lslam_matcher_rows_mfma_launches
+ *    counts those that took the MFMA accumulate.  The one-launch kernels (LSLAM_OPT_STEP_KERNEL / LSLAM_OPT_LONE_KERNEL),
+ *    the LDS-staged experiment and rows of up to 4 positions keep the packed form. */
 enum { LSLAM_OPT_ROW_OCCUPANCY = 1, LSLAM_OPT_COLLECT_STATS = 2, LSLAM_OPT_LDS_STAGED = 3, LSLAM_OPT_PIPELINE_DEPTH = 4,
-       LSLAM_OPT_STEP_KERNEL = 5, LSLAM_OPT_STEP_MIN_SCANS = 6, LSLAM_OPT_ROWS_WAVES = 7, LSLAM_OPT_CHECK_OUTPUT_REUSE = 8, LSLAM_OPT_LONE_KERNEL = 9 };
+       LSLAM_OPT_STEP_KERNEL = 5, LSLAM_OPT_STEP_MIN_SCANS = 6, LSLAM_OPT_ROWS_WAVES = 7, LSLAM_OPT_CHECK_OUTPUT_REUSE = 8, LSLAM_OPT_LONE_KERNEL = 9,
+       LSLAM_OPT_ROWS_MFMA = 10 };
 /* current value of an option (negative: error code) */
 int lslam_matcher_get_option(const lslam_matcher* m, int option);
 /* Order the context stream behind every pipelined step in flight (no host wait).  No-op at depth 1. */
@@ -213,6 +223,8 @@ int64_t lslam_matcher_pipelined_steps(const lslam_matcher* m);
 int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m);
 /* diagnostics: single-scan matches that went out as ONE launch (LSLAM_OPT_LONE_KERNEL) so far */
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m);
+/* diagnostics: k_resp_rows / k_resp_rows_mw launches that took the MFMA accumulate (LSLAM_OPT_ROWS_MFMA) so far */
+int64_t lslam_matcher_rows_mfma_launches(const lslam_matcher* m);
 /* diagnostics: which FORM of the response kernel took the passes of the matches so far.  Every coarse form goes out under
  * the same profile name (resp_rows_coarse), and the dispatch falls back silently (a batch below the tiled planes' threshold,
  * more than 2048 beams, planes that could not be allocated ...): a test or an A/B run that selects a form with

@@ -5,7 +5,7 @@ counts with the source lines the VALU instructions come from.  With --phases 'na
 named.  The dynamic budget of k_resp_rows (profiles/r05/inst_budget_resp_rows.md) multiplies these blocks by the trip
 counts the instrumented twin of the kernel measures (lslam_matcher_read_stats).
 
-    python tools/inst_budget.py --kernel 'k_resp_rowsILi3ELi11ELb1ELb0ELb0E' \
+    python tools/inst_budget.py --kernel 'k_resp_rowsILi3ELi11ELb1ELb1ELb0ELb0E' \
         --phases 'B_drain:511-604,A_cell:635-687,A_emit:688-746,A_estimate:749-783,parked:785-792,A_loop:793-805,parked_loop:806-814,epilogue:846-885'
 """
 import argparse, collections, pathlib, re, subprocess, sys, tempfile

@@ -15,6 +15,8 @@ import json
 import sys
 
 NAMES = {  # rocprofv3 kernel name prefix -> the name bench.py's HIP-event timer uses
+    "k_resp_rows<3, 11, true, true, false, false>": "resp_rows_coarse",   # <NXD, NYC, TILED, MFMA, STATS, LDSB>: the MFMA form
+    "k_resp_rows<3, 11, true, false, false, false>": "resp_rows_coarse",  # the packed form (rows_mfma 0, bytes above 127)
     "k_resp_rows<3, 11, true, false, false>": "resp_rows_coarse",
     "k_resp_rows<3, 11, true, false>": "resp_rows_coarse",
     "k_resp_rows<3, 11, true>": "resp_rows_coarse",

@@ -40,7 +40,9 @@ def main(pmc_path, scans):
               f"A_estimate:{m['estimate']}-{m['point'] - 1},A_point:{m['point']}-{m['exact'] - 1},parked:{m['exact']}-{m['loop'] - 1},"
               f"A_loop:{m['loop']}-{m['epi'] - 1},epilogue:{m['epi']}-{m['end']}")
     out = {}
-    jobs = [("resp_rows_coarse", "k_resp_rows<3, 11, true", "k_resp_rowsILi3ELi11ELb1ELb0ELb0E", phases,
+    # the PACKED form of the coarse kernel (<3, 11, TILED, MFMA = false, STATS, LDSB>): the per-phase dynamic counts below were
+    # measured on it, so the counter passes fed in here have to be taken with set_option("rows_mfma", 0)
+    jobs = [("resp_rows_coarse", "k_resp_rows<3, 11, true, false", "k_resp_rowsILi3ELi11ELb1ELb0ELb0ELb0E", phases,
              "A_cell+A_emit+A_estimate+A_point+A_loop:1080,B_drain:1016,epilogue:283,parked:50,other:51")]
     t0 = line_of(src, "__device__ __forceinline__ void resp_tile3_wave(")
     t1 = line_of(src, "k_resp_tile3(const uint4* __restrict__ tiles", t0)

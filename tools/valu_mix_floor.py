@@ -20,7 +20,7 @@ average cycles of that phase's instructions:
 No clock is assumed anywhere: cycles on both sides.  An opcode the table does not know is priced FAST (so the result stays a
 floor).  Output: JSON on stdout, the table on stderr.
 
-    python tools/valu_mix_floor.py --kernel k_resp_rowsILi3ELi11ELb1ELb0ELb0E \\
+    python tools/valu_mix_floor.py --kernel k_resp_rowsILi3ELi11ELb1ELb0ELb0ELb0E \\
         --phases 'B_drain:543-645,A_cell:671-728,A_emit:729-798,A_estimate:799-831,A_point:832-839,parked:840-847,A_loop:848-944,epilogue:945-990' \\
         --dyn 'A_cell+A_emit+A_estimate+A_point+A_loop:1080,B_drain:1016,epilogue:283,parked:50,other:51' \\
         --waves 86016 --measured-cycles 971364 --valu-per-wave 2417.1
