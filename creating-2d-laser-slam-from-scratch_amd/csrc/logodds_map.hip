@@ -2237,6 +2237,10 @@ int update_batch_dev_impl(lslam_map* map, int n_scans, const float* points_xy_de
                           const float* origos_xy, const float* poses_world, const float* radius, bool use_hint) {
   lslam_context* ctx = map->ctx;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // a call is applied whole or not at all: a scan that a later group of 64 would refuse is refused before the first group runs
+  for (int k = 0; k < n_scans; k++)
+    if (n_points[k] < 0 || n_points[k] > kMaxBeams)
+      return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per scan are supported (got %d)", kMaxBeams, n_points[k]);
   size_t done_pts = 0;
   for (int k0 = 0; k0 < n_scans; k0 += kBatchMaxScans) {
     const int K = std::min(kBatchMaxScans, n_scans - k0);
