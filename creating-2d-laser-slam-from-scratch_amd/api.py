@@ -457,6 +457,12 @@ def lib() -> C.CDLL:
     L.lslam_map_match_data.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.lslam_map_match_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.lslam_map_match_batch_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    for f in ("lslam_map_score_batch", "lslam_map_score_batch_dev"):
+        getattr(L, f).argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+    for f in ("lslam_map_pose_covariance_batch", "lslam_map_pose_covariance_batch_dev"):
+        getattr(L, f).argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    for f in ("lslam_map_score_lattice", "lslam_map_score_lattice_dev"):
+        getattr(L, f).argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
     L.lslam_map_cached_points.argtypes = [vp]
     L.lslam_map_set_option.argtypes = [vp, i32, i32]
     L.lslam_map_batch_stats.argtypes = [vp, vp]
@@ -1541,6 +1547,111 @@ class OccGridMap:
         self.ctx.check(self.L.lslam_map_match_batch_dev(self.h, n_entries, len(counts), points_ptr, counts.ctypes.data,
                                                         None if ec is None else ec.ctypes.data, begin_ptr, poses_ptr,
                                                         covs_ptr or None))
+
+    @staticmethod
+    def _pack(containers, counts):
+        """-> (packed points [sum, 2] float32, counts int32) of a list of containers, or of one packed array with `counts`."""
+        if counts is None:
+            counts = np.array([len(p) for p in containers], dtype=np.int32)
+            pts = (np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in containers])
+                   if len(containers) else np.zeros((0, 2), np.float32))
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            pts = np.asarray(containers, dtype=np.float32).reshape(-1, 2)
+        return np.ascontiguousarray(pts, dtype=np.float32), counts
+
+    def scoreBatch(self, poses_world, containers, entry_container=None, counts=None, level: int = 0):
+        """getResidualForState / getLikelihoodForState (OccGridMapUtil.h:342-374) of many (container, world pose) pairs on
+        one level of the map as it is -> (residual[B], likelihood[B]).  Containers as for matchBatch.  A pure query."""
+        pts, counts = self._pack(containers, counts)
+        w = np.ascontiguousarray(poses_world, dtype=np.float32).reshape(-1, 3)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        res, lik = np.zeros(len(w), np.float32), np.zeros(len(w), np.float32)
+        self.ctx.check(self.L.lslam_map_score_batch(self.h, len(w), len(counts), pts.ctypes.data, counts.ctypes.data,
+                                                    None if ec is None else ec.ctypes.data, w.ctypes.data, int(level),
+                                                    res.ctypes.data, lik.ctypes.data))
+        return res, lik
+
+    def scoreBatch_dev(self, n_entries: int, points_ptr: int, counts, entry_container, poses_ptr: int, level: int,
+                       residual_ptr: int, likelihood_ptr: int):
+        """scoreBatch on device pointers (residual_ptr may be 0); asynchronous on the context stream."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        self.ctx.check(self.L.lslam_map_score_batch_dev(self.h, n_entries, len(counts), points_ptr, counts.ctypes.data,
+                                                        None if ec is None else ec.ctypes.data, poses_ptr, int(level),
+                                                        residual_ptr or None, likelihood_ptr or None))
+
+    def poseCovarianceBatch(self, poses_world, containers, entry_container=None, counts=None, level: int = 0):
+        """getCovarianceForPose + getCovMatrixWorldCoords (OccGridMapUtil.h:249-339) per (container, world pose) ->
+        (likelihoods[B,7] of the sigma points, cov_map[B,3,3] in level cells / rad, cov_world[B,3,3] in m / rad)."""
+        pts, counts = self._pack(containers, counts)
+        w = np.ascontiguousarray(poses_world, dtype=np.float32).reshape(-1, 3)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        lik = np.zeros((len(w), 7), np.float32)
+        cm, cw = np.zeros((len(w), 9), np.float32), np.zeros((len(w), 9), np.float32)
+        self.ctx.check(self.L.lslam_map_pose_covariance_batch(self.h, len(w), len(counts), pts.ctypes.data, counts.ctypes.data,
+                                                              None if ec is None else ec.ctypes.data, w.ctypes.data,
+                                                              int(level), lik.ctypes.data, cm.ctypes.data, cw.ctypes.data))
+        return lik, cm.reshape(-1, 3, 3), cw.reshape(-1, 3, 3)
+
+    def poseCovarianceBatch_dev(self, n_entries: int, points_ptr: int, counts, entry_container, poses_ptr: int, level: int,
+                                likelihoods_ptr: int, cov_map_ptr: int = 0, cov_world_ptr: int = 0):
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        ec = None if entry_container is None else np.ascontiguousarray(entry_container, dtype=np.int32)
+        self.ctx.check(self.L.lslam_map_pose_covariance_batch_dev(
+            self.h, n_entries, len(counts), points_ptr, counts.ctypes.data, None if ec is None else ec.ctypes.data, poses_ptr,
+            int(level), likelihoods_ptr or None, cov_map_ptr or None, cov_world_ptr or None))
+
+    @staticmethod
+    def lattice_poses(centre_world, counts, steps) -> np.ndarray:
+        """The world poses scoreLattice evaluates, [nt * ny * nx, 3] float32 in the volume's order, by its own expression."""
+        c = np.asarray(centre_world, np.float32)
+        d = np.asarray(steps, np.float32)
+        nx, ny, nt = (int(v) for v in counts)
+        ax = [c[a] + (np.arange(n, dtype=np.int64) - n // 2).astype(np.float32) * d[a] for a, n in enumerate((nx, ny, nt))]
+        out = np.zeros((nt, ny, nx, 3), np.float32)
+        out[..., 0] = ax[0][None, None, :]
+        out[..., 1] = ax[1][None, :, None]
+        out[..., 2] = ax[2][:, None, None]
+        return out.reshape(-1, 3)
+
+    def scoreLattice(self, points_xy, centre_world, counts, steps, level: int = 0):
+        """Likelihoods of one container over a lattice of world poses around centre_world (counts = (nx, ny, nt), steps =
+        (dx, dy, dtheta)) -> (volume[nt, ny, nx], best linear index or -1, best likelihood)."""
+        p = np.ascontiguousarray(points_xy, dtype=np.float32).reshape(-1, 2)
+        c = np.ascontiguousarray(centre_world, dtype=np.float32)
+        n3 = np.ascontiguousarray(counts, dtype=np.int32)
+        d = np.ascontiguousarray(steps, dtype=np.float32)
+        assert c.shape == (3,) and n3.shape == (3,) and d.shape == (3,)
+        vol = np.zeros(max(int(n3[0]), 0) * max(int(n3[1]), 0) * max(int(n3[2]), 0), np.float32)
+        bi, bl = C.c_int32(0), C.c_float(0.0)
+        self.ctx.check(self.L.lslam_map_score_lattice(self.h, p.ctypes.data, p.shape[0], c.ctypes.data, n3.ctypes.data,
+                                                      d.ctypes.data, int(level), vol.ctypes.data, C.addressof(bi), C.addressof(bl)))
+        return vol.reshape(int(n3[2]), int(n3[1]), int(n3[0])), bi.value, np.float32(bl.value)
+
+    def scoreLattice_dev(self, points_ptr: int, n: int, centre_world, counts, steps, level: int, volume_ptr: int,
+                         best_index_ptr: int = 0, best_likelihood_ptr: int = 0):
+        c = np.ascontiguousarray(centre_world, dtype=np.float32)
+        n3 = np.ascontiguousarray(counts, dtype=np.int32)
+        d = np.ascontiguousarray(steps, dtype=np.float32)
+        self.ctx.check(self.L.lslam_map_score_lattice_dev(self.h, points_ptr, n, c.ctypes.data, n3.ctypes.data, d.ctypes.data,
+                                                          int(level), volume_ptr or None, best_index_ptr or None,
+                                                          best_likelihood_ptr or None))
+
+    def relocalise(self, container, centre_world, counts, steps, level: int, k: int):
+        """Global-then-local: score the lattice on `level`, start matchBatch from its k best states, score the k matched
+        poses on level 0 -> (poses[k,3], likelihoods[k], covs[k,3,3]) sorted by likelihood, best first."""
+        p = np.ascontiguousarray(container, dtype=np.float32).reshape(-1, 2)
+        vol, _, _ = self.scoreLattice(p, centre_world, counts, steps, level)
+        flat = vol.reshape(-1)
+        order = np.argsort(-np.where(np.isnan(flat), -np.inf, flat), kind="stable")[:max(int(k), 0)]
+        starts = self.lattice_poses(centre_world, counts, steps)[order]
+        if not len(starts):
+            return np.zeros((0, 3), np.float32), np.zeros(0, np.float32), np.zeros((0, 3, 3), np.float32)
+        poses, covs = self.matchBatch(starts, [p], entry_container=np.zeros(len(starts), np.int32))
+        _, lik = self.scoreBatch(poses, [p], entry_container=np.zeros(len(starts), np.int32), level=0)
+        best = np.argsort(-np.where(np.isnan(lik), -np.inf, lik), kind="stable")
+        return poses[best], lik[best], covs[best]
 
     def set_option(self, name: str, value: int):
         """'ordered_sums': matchData adds its sums in point order (bit-equal to the CPU restatement) instead of in parallel."""

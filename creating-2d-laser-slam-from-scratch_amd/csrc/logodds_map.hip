@@ -1245,6 +1245,245 @@ k_gn_match_batch_ordered(GnLevels lv, const float* __restrict__ pts, const int2*
                    out_cov ? out_cov + 9 * (size_t)e : (float*)nullptr);
 }
 
+// ------------------------------------------------------------------------------------------
+// POSE SCORING (lslam_map_score_batch / lslam_map_pose_covariance_batch / lslam_map_score_lattice): how well a container
+// fits one level of the map at a pose -- OccGridMapUtil::getResidualForState / getLikelihoodForState / getCovarianceForPose
+// / getCovMatrixWorldCoords (H/map/OccGridMapUtil.h:249-374) with interpMapValue (:379-434).  A STATE is (container, pose
+// on the level's raster, level); its residual is the sum over the container of 1 - interpMapValue(T(pose) * p * 2^-level),
+// its likelihood 1 - residual / n.  Three forms feed ONE scoring kernel, which asks ms_state for the pose of state `st`:
+//   batch     state e is entry e's world pose
+//   cov       state 7 e + k is sigma point k of entry e (getCovarianceForPose's order); k_ms_cov, enqueued behind the scoring
+//             launch, turns the seven likelihoods into the weighted covariance -- no host round trip in between
+//   lattice   state (k * ny + j) * nx + i is the centre pose plus (i - nx/2, j - ny/2, k - nt/2) steps, evaluated on the
+//             device (no pose array goes up); k_ms_best then finds the best state
+// and ms_point is the one statement of a point's term (value only: no gradient, no nine products).
+// Default mode, k_ms_score: ONE WAVE per state, kMsWaves states per block, as k_gn_match_batch -- no LDS, no barrier.  Lane l
+// adds the terms of points l, l + 64, l + 128 ... in that order and gn_wave_sum adds the 64 partials, so a state's result is
+// a function of its container, its pose and the map: not of the batch, the block, the form or the chunk size CH (the
+// number of points per lane whose cell loads are in flight together).  Hardware exp / rcp (gn_prob_f), ocml sincosf (one
+// call per state; a scoring caller's heading is not bounded the way gn_sincos asks).
+// Ordered mode, k_ms_score_ordered: one block per state; the threads evaluate the terms of a chunk of points into LDS with the
+// ordered matcher's gn_prob and double sin / cos, ONE thread adds them in container order like the reference's loop
+// (:366-371).  A float per point and a fixed chunk: any container the map accepts.
+// ------------------------------------------------------------------------------------------
+constexpr int kMsBatch = 0, kMsCov = 1, kMsLattice = 2;
+struct MsJob {
+  int mode, n_states;
+  const float* lo;      // the level: its plane, size, world -> raster scaling (gn_level_begin), the container's scaling
+  int sx, sy;
+  float scale, t_x, t_y, factor, cell_length;
+  const float* poses;   // batch, cov: [n_entries][3] world poses
+  const int2* ent;      // batch, cov: [n_entries] (first point, points)
+  int first, n;         // lattice: its one container
+  float c0, c1, c2, d0, d1, d2;  // lattice: centre world pose, steps
+  int nx, ny, nt;
+  float* out_res;       // batch: [n_states], may be null
+  float* out_lik;       // [n_states]: batch's likelihoods, cov's [n_entries][7], the lattice's volume
+};
+
+// sigma point k of getCovarianceForPose (OccGridMapUtil.h:252-268) around a pose on the level's raster; 6 is the pose itself
+__device__ __forceinline__ void ms_sigma_point(int k, float x, float y, float ang, float& e0, float& e1, float& e2) {
+  e0 = k == 0 ? x + 1.5f : (k == 1 ? x - 1.5f : x);
+  e1 = k == 2 ? y + 1.5f : (k == 3 ? y - 1.5f : y);
+  e2 = k == 4 ? ang + 0.05f : (k == 5 ? ang - 0.05f : ang);
+}
+
+// state st of a job: its container and its pose on the level's raster
+__device__ __forceinline__ void ms_state(const MsJob& J, int st, int2& en, float& e0, float& e1, float& e2) {
+  float w0, w1, w2;
+  int sigma = 6;
+  if (J.mode == kMsLattice) {
+    const int i = st % J.nx, j = (st / J.nx) % J.ny, k = st / (J.nx * J.ny);
+    w0 = J.c0 + (float)(i - J.nx / 2) * J.d0;
+    w1 = J.c1 + (float)(j - J.ny / 2) * J.d1;
+    w2 = J.c2 + (float)(k - J.nt / 2) * J.d2;
+    en = make_int2(J.first, J.n);
+  } else {
+    const int e = J.mode == kMsCov ? st / 7 : st;
+    if (J.mode == kMsCov) sigma = st - 7 * e;
+    w0 = J.poses[3 * (size_t)e]; w1 = J.poses[3 * (size_t)e + 1]; w2 = J.poses[3 * (size_t)e + 2];
+    en = J.ent[e];
+  }
+  float x, y, ang;
+  gn_level_begin(J.scale, J.t_x, J.t_y, w0, w1, w2, x, y, ang);
+  ms_sigma_point(sigma, x, y, ang, e0, e1, e2);
+}
+
+// one point's term of getResidualForState (:369): 1 - interpMapValue(transform * p).  A point outside the map reads cell 0
+// and is masked (value 0, :382-385), so no load sits behind a branch.  ORDERED: the ordered matcher's gn_prob (exp in double).
+template <bool ORDERED>
+__device__ __forceinline__ float ms_point(const float* __restrict__ lo, int sx, float lim_x, float lim_y, float s, float c, float e0,
+                                          float e1, float px, float py) {
+  const float cx = (c * px + (-s) * py) + e0;
+  const float cy = (s * px + c * py) + e1;
+  const bool in_map = !(cx < 0.0f || cx > lim_x || cy < 0.0f || cy > lim_y);  // pointOutOfMapBounds (:60-63)
+  const int ix = in_map ? (int)cx : 0, iy = in_map ? (int)cy : 0;
+  const int index = iy * sx + ix;
+  float o[3];
+  if (ORDERED) {
+    gn_interp(gn_prob(lo, index), gn_prob(lo, index + 1), gn_prob(lo, index + sx), gn_prob(lo, index + sx + 1), cx - (float)ix,
+              cy - (float)iy, in_map, o);
+  } else {
+    const float l0 = lo[index], l1 = lo[index + 1], l2 = lo[index + sx], l3 = lo[index + sx + 1];
+    gn_interp(gn_prob_f(l0), gn_prob_f(l1), gn_prob_f(l2), gn_prob_f(l3), cx - (float)ix, cy - (float)iy, in_map, o);
+  }
+  return 1.0f - o[0];
+}
+
+// getLikelihoodForResidual (:349-355); an empty container: 0 / 0
+__device__ __forceinline__ void ms_write(const MsJob& J, int st, float residual, int n) {
+  if (J.out_res) J.out_res[st] = residual;
+  J.out_lik[st] = 1.0f - (residual / (float)n);
+}
+
+constexpr int kMsWaves = 4;  // states per block
+
+template <int CH>
+__global__ void __launch_bounds__(64 * kMsWaves) __attribute__((amdgpu_waves_per_eu(4)))
+k_ms_score(MsJob J, const float* __restrict__ pts) {
+  const int lane = threadIdx.x & 63;
+  const int st = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kMsWaves + (threadIdx.x >> 6)));
+  if (st >= J.n_states) return;  // (whole waves: nothing below waits for another wave)
+  int2 en;
+  float e0, e1, e2;
+  ms_state(J, st, en, e0, e1, e2);
+  const int first = __builtin_amdgcn_readfirstlane(en.x), n = __builtin_amdgcn_readfirstlane(en.y);
+  const float2* __restrict__ P = reinterpret_cast<const float2*>(pts) + first;
+  const float* __restrict__ lo = in_device_memory(J.lo);
+  const int sx = J.sx;
+  const float lim_x = (float)J.sx - 2.0f, lim_y = (float)J.sy - 2.0f;  // MapDimensionProperties.h:66-70
+  const float factor = J.factor;
+  float s, c;
+  sincosf(e2, &s, &c);
+  float acc = 0.0f;
+  for (int base = 0; base < n; base += 64 * CH) {  // (n is wave-uniform: no lane leaves the loop early)
+    float px[CH], py[CH];
+    bool have[CH];
+#pragma unroll
+    for (int j = 0; j < CH; j++) {
+      const int i = base + 64 * j + lane;
+      have[j] = i < n;
+      float2 v = make_float2(0.0f, 0.0f);
+      if (have[j]) v = P[i];
+      px[j] = v.x * factor;
+      py[j] = v.y * factor;
+    }
+#pragma unroll
+    for (int j = 0; j < CH; j++) {
+      const float f = ms_point<false>(lo, sx, lim_x, lim_y, s, c, e0, e1, px[j], py[j]);
+      acc += have[j] ? f : 0.0f;
+    }
+  }
+  const float residual = gn_wave_sum(acc);
+  if (lane == 0) ms_write(J, st, residual, n);
+}
+
+constexpr int kMsOrderedChunk = 4096;  // terms in LDS at a time
+
+__global__ void __launch_bounds__(256)
+k_ms_score_ordered(MsJob J, const float* __restrict__ pts) {
+  __shared__ float s_term[kMsOrderedChunk];
+  const int tid = threadIdx.x, st = blockIdx.x;
+  int2 en;
+  float e0, e1, e2;
+  ms_state(J, st, en, e0, e1, e2);
+  const int n = en.y;
+  const float2* __restrict__ P = reinterpret_cast<const float2*>(pts) + en.x;
+  const float* __restrict__ lo = in_device_memory(J.lo);
+  const float lim_x = (float)J.sx - 2.0f, lim_y = (float)J.sy - 2.0f;
+  const float c = (float)cos((double)e2), s = (float)sin((double)e2);  // getTransformForState (:437-440)
+  float residual = 0.0f;  // thread 0's
+  for (int base = 0; base < n; base += kMsOrderedChunk) {
+    const int m = min(kMsOrderedChunk, n - base);
+    for (int i = tid; i < m; i += 256) {
+      const float2 v = P[base + i];
+      s_term[i] = ms_point<true>(lo, J.sx, lim_x, lim_y, s, c, e0, e1, v.x * J.factor, v.y * J.factor);
+    }
+    __syncthreads();
+    if (tid == 0) {  // residual += funval, in container order (:366-371)
+#pragma unroll 8
+      for (int i = 0; i < m; i++) residual += s_term[i];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) ms_write(J, st, residual, n);
+}
+
+// The lattice's best state: the highest likelihood, the lowest linear index among equals, NaN never; -1 / NaN when there
+// is none.  One block: a thread walks its states in rising order, the waves and then the block meet pairwise.
+__device__ __forceinline__ void ms_better(float v, int i, float& bv, int& bi) {
+  if (i >= 0 && (bi < 0 || v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+}
+__global__ void __launch_bounds__(1024)
+k_ms_best(const float* __restrict__ vol, int n, int* __restrict__ out_index, float* __restrict__ out_lik) {
+  __shared__ float s_v[16];
+  __shared__ int s_i[16];
+  const int tid = threadIdx.x;
+  float bv = 0.0f;
+  int bi = -1;
+  for (int i = tid; i < n; i += 1024) {
+    const float v = vol[i];
+    if (v == v) ms_better(v, i, bv, bi);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) ms_better(__shfl_xor(bv, d), __shfl_xor(bi, d), bv, bi);
+  if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; w++) ms_better(s_v[w], s_i[w], bv, bi);
+    if (out_index) *out_index = bi;
+    if (out_lik) *out_lik = bi < 0 ? __int_as_float(0x7fc00000) : bv;
+  }
+}
+
+// getCovarianceForPose's weighted mean and covariance (OccGridMapUtil.h:280-302) from an entry's seven likelihoods, then
+// getCovMatrixWorldCoords (:314-339); one thread per entry.  The orders are Eigen's for these fixed sizes: the 7-term sum()
+// in halves -- (l0 + (l1 + l2)) + ((l3 + l4) + (l5 + l6)) --, += coefficient by coefficient, the outer product d d^T first and
+// the scalar weight in front of it.
+__global__ void __launch_bounds__(256)
+k_ms_cov(MsJob J, int n_entries, const float* __restrict__ lik /* [n_entries][7] */, float* __restrict__ cov_map,
+         float* __restrict__ cov_world) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_entries) return;
+  float x, y, ang;
+  gn_level_begin(J.scale, J.t_x, J.t_y, J.poses[3 * (size_t)e], J.poses[3 * (size_t)e + 1], J.poses[3 * (size_t)e + 2], x, y, ang);
+  float sp[7][3], l[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    ms_sigma_point(k, x, y, ang, sp[k][0], sp[k][1], sp[k][2]);
+    l[k] = lik[7 * (size_t)e + k];
+  }
+  const float inv = 1.0f / ((l[0] + (l[1] + l[2])) + ((l[3] + l[4]) + (l[5] + l[6])));
+  float mean[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < 7; k++)
+#pragma unroll
+    for (int r = 0; r < 3; r++) mean[r] += sp[k][r] * l[k];
+#pragma unroll
+  for (int r = 0; r < 3; r++) mean[r] *= inv;
+  float m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    const float d[3] = {sp[k][0] - mean[0], sp[k][1] - mean[1], sp[k][2] - mean[2]};
+    const float w = l[k] * inv;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int q = 0; q < 3; q++) m[3 * r + q] += w * (d[r] * d[q]);
+  }
+  if (cov_map)
+    for (int q = 0; q < 9; q++) cov_map[9 * (size_t)e + q] = m[q];
+  if (cov_world) {
+    const float sc = J.cell_length, sq = sc * sc;
+    float* w = cov_world + 9 * (size_t)e;
+    w[0] = m[0] * sq; w[4] = m[4] * sq;
+    w[3] = m[3] * sq; w[1] = w[3];
+    w[6] = m[6] * sc; w[2] = w[6];
+    w[7] = m[7] * sc; w[5] = w[7];
+    w[8] = m[8];
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------
 // STREAMED HectorSlamProcessor (lslam_hector_*): HectorSlamProcessor::update (H/slam_main/HectorSlamProcessor.h:81-108) for a
@@ -1598,6 +1837,10 @@ struct lslam_map {
   // lslam_map_match_batch*: the entry table (first point, points), and -- host form -- the start poses in, 12 floats per entry out
   DevBuf<int2> d_gnb_ent;
   DevBuf<float> d_gnb_io;
+  // lslam_map_score_* / lslam_map_pose_covariance_batch, host forms: poses in, residuals / likelihoods / covariances / the
+  // lattice's volume out (the entry table is d_gnb_ent)
+  DevBuf<float> d_score_io;
+  int score_chunk = 4;        // LSLAM_SCORE_CHUNK = 2 | 4 | 8: points per lane in flight in k_ms_score (results do not depend on it)
   // matchData, parallel-sum kernel (the default): the container goes up through pinned memory and is read -- and cached in
   // d_cached -- by the kernel itself; its 12 result floats land in pinned memory.  ordered_sums: k_gn_match instead.
   // batched update: scratch budget of the tile-slot pools of ONE level (bytes), rounds used by the last call, cells
@@ -1871,6 +2114,8 @@ int lslam_map_create(lslam_context* ctx, int size_x, int size_y, float cell_leng
     map->ordered_sums = e && e[0] == '1';
     e = getenv("LSLAM_GN_THREADS");
     if (e && atoi(e) >= 256) map->gn_threads = atoi(e);
+    e = getenv("LSLAM_SCORE_CHUNK");
+    if (e && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) map->score_chunk = atoi(e);
   }
   (void)hipStreamSynchronize(ctx->stream);
   ctx->pre_sync.emplace_back((void*)map, [](void* m) { return lslam_map_flush((lslam_map*)m); });  // lslam_synchronize flushes
@@ -1923,6 +2168,7 @@ void lslam_map_destroy(lslam_map* map) {
   map->d_gn_out.release();
   map->d_gnb_ent.release();
   map->d_gnb_io.release();
+  map->d_score_io.release();
   map->d_hash.release();
   map->d_hdr.release();
   map->d_scan.release();
@@ -2729,6 +2975,279 @@ int lslam_map_match_batch(lslam_map* map, int n_entries, int n_containers, const
   LSLAM_HIP(ctx, hipMemcpyAsync(out_poses, d_pose, 3 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   if (out_covs) LSLAM_HIP(ctx, hipMemcpyAsync(out_covs, d_cov, 9 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // one wait for the whole batch
+  return LSLAM_OK;
+}
+
+namespace {
+// ---- pose scoring (k_ms_*).  Like the batched match: everything that can be refused is refused before anything is enqueued
+// or written, and nothing here touches a plane, d_cached or n_cached.
+constexpr int kMsMaxStates = 1 << 24;  // per call (the lattice's volume, 7 x the covariance entries)
+
+int score_level_check(lslam_map* map, const char* who, int level) {
+  lslam_context* ctx = map->ctx;
+  if (level < 0 || level >= (int)map->levels.size())
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: level %d is outside the pyramid (%d levels)", who, level, (int)map->levels.size());
+  if (map->levels[level].sx < 2 || map->levels[level].sy < 2)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: level %d is smaller than 2 x 2 cells", who, level);
+  return LSLAM_OK;
+}
+
+int score_check(lslam_map* map, const char* who, int n_entries, int states_per_entry, int n_containers, const void* points_xy,
+                const int32_t* n_points, const int32_t* entry_container, const void* poses_world, const void* out, int level,
+                size_t* total_out) {
+  lslam_context* ctx = map->ctx;
+  if (n_entries < 0 || n_containers < 0)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: negative count (n_entries %d, n_containers %d)", who, n_entries, n_containers);
+  *total_out = 0;
+  if (n_entries == 0) return LSLAM_OK;
+  if (!poses_world || !out) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: poses_world and the likelihood output are required", who);
+  if (n_containers > 0 && !n_points) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: n_points is required", who);
+  if (!entry_container && n_containers != n_entries)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: without entry_container entry i uses container i, so n_containers (%d) must equal n_entries (%d)",
+                     who, n_containers, n_entries);
+  {
+    int rc = score_level_check(map, who, level);
+    if (rc) return rc;
+  }
+  if (n_entries > kMsMaxStates / states_per_entry)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d entries per call", who, kMsMaxStates / states_per_entry);
+  size_t total = 0;
+  for (int k = 0; k < n_containers; k++) {
+    const int n = n_points[k];
+    if (n < 0) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: container %d has a negative point count (%d)", who, k, n);
+    if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per scan are supported (got %d)", kMaxBeams, n);
+    total += (size_t)n;
+  }
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "batch too large");
+  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: points_xy is required", who);
+  if (entry_container)
+    for (int e = 0; e < n_entries; e++)
+      if (entry_container[e] < 0 || entry_container[e] >= n_containers)
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: entry %d names container %d of %d", who, e, entry_container[e], n_containers);
+  *total_out = total;
+  return LSLAM_OK;
+}
+
+MsJob score_job(const lslam_map* map, int level, int mode, int n_states) {
+  const Level& L = map->levels[level];
+  MsJob J{};
+  J.mode = mode; J.n_states = n_states;
+  J.lo = L.d_logodds; J.sx = L.sx; J.sy = L.sy;
+  J.scale = L.scale_to_map; J.t_x = L.t_x; J.t_y = L.t_y; J.cell_length = L.cell_length;
+  J.factor = level == 0 ? 1.0f : 1.0f / (float)(1 << level);  // DataContainer::setFrom (MapRepMultiMap.h:161), as the matcher
+  return J;
+}
+
+// the entry table (first point, points) of a batch -> d_gnb_ent
+int score_entries(lslam_map* map, int n_entries, int n_containers, const int32_t* n_points, const int32_t* entry_container) {
+  lslam_context* ctx = map->ctx;
+  std::vector<int> first((size_t)n_containers + 1, 0);
+  for (int k = 0; k < n_containers; k++) first[k + 1] = first[k] + n_points[k];
+  std::vector<int2> ent((size_t)n_entries);
+  for (int e = 0; e < n_entries; e++) {
+    const int k = entry_container ? entry_container[e] : e;
+    ent[e] = make_int2(first[k], n_points[k]);
+  }
+  LSLAM_HIP(ctx, map->d_gnb_ent.reserve((size_t)n_entries));
+  LSLAM_HIP(ctx, hipMemcpyAsync(map->d_gnb_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+  return LSLAM_OK;
+}
+
+int score_launch(lslam_map* map, const MsJob& J, const float* d_pts) {
+  lslam_context* ctx = map->ctx;
+  if (map->ordered_sums) {
+    launch(ctx, "ms_score", k_ms_score_ordered, dim3((unsigned)J.n_states), dim3(256), 0, J, d_pts);
+  } else {
+    const dim3 grid((unsigned)((J.n_states + kMsWaves - 1) / kMsWaves)), block(64 * kMsWaves);
+    if (map->score_chunk == 2) launch(ctx, "ms_score", k_ms_score<2>, grid, block, 0, J, d_pts);
+    else if (map->score_chunk == 8) launch(ctx, "ms_score", k_ms_score<8>, grid, block, 0, J, d_pts);
+    else launch(ctx, "ms_score", k_ms_score<4>, grid, block, 0, J, d_pts);
+  }
+  LSLAM_HIP(ctx, hipGetLastError());
+  return LSLAM_OK;
+}
+
+int score_batch_launch(lslam_map* map, int n_entries, int n_containers, const float* d_pts, const int32_t* n_points,
+                       const int32_t* entry_container, const float* d_poses, int level, float* d_res, float* d_lik) {
+  int rc = flush_pending(map);  // the kernels read the float planes
+  if (rc) return rc;
+  rc = score_entries(map, n_entries, n_containers, n_points, entry_container);
+  if (rc) return rc;
+  MsJob J = score_job(map, level, kMsBatch, n_entries);
+  J.poses = d_poses; J.ent = map->d_gnb_ent.p; J.out_res = d_res; J.out_lik = d_lik;
+  return score_launch(map, J, d_pts);
+}
+
+int score_cov_launch(lslam_map* map, int n_entries, int n_containers, const float* d_pts, const int32_t* n_points,
+                     const int32_t* entry_container, const float* d_poses, int level, float* d_lik, float* d_cov_map,
+                     float* d_cov_world) {
+  lslam_context* ctx = map->ctx;
+  int rc = flush_pending(map);
+  if (rc) return rc;
+  rc = score_entries(map, n_entries, n_containers, n_points, entry_container);
+  if (rc) return rc;
+  MsJob J = score_job(map, level, kMsCov, 7 * n_entries);
+  J.poses = d_poses; J.ent = map->d_gnb_ent.p; J.out_lik = d_lik;
+  rc = score_launch(map, J, d_pts);
+  if (rc || (!d_cov_map && !d_cov_world)) return rc;
+  launch(ctx, "ms_cov", k_ms_cov, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, J, n_entries, (const float*)d_lik,
+         d_cov_map, d_cov_world);
+  LSLAM_HIP(ctx, hipGetLastError());
+  return LSLAM_OK;
+}
+
+int score_lattice_check(lslam_map* map, const char* who, const void* points_xy, int n, const float* centre_world,
+                        const int32_t* counts, const float* steps, int level, const void* out_volume, int* n_states) {
+  lslam_context* ctx = map->ctx;
+  if (n < 0 || (n > 0 && !points_xy) || !centre_world || !counts || !steps || !out_volume)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: points_xy, centre_world, counts, steps and out_volume are required", who);
+  if (counts[0] <= 0 || counts[1] <= 0 || counts[2] <= 0)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: lattice counts must be positive (got %d x %d x %d)", who, counts[0], counts[1], counts[2]);
+  int rc = score_level_check(map, who, level);
+  if (rc) return rc;
+  if (n > kMaxBeams) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "at most %d points per scan are supported (got %d)", kMaxBeams, n);
+  const long long states = (long long)counts[0] * counts[1] * counts[2];
+  if (counts[0] > kMsMaxStates || counts[1] > kMsMaxStates || (long long)counts[0] * counts[1] > kMsMaxStates || states > kMsMaxStates)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d lattice states per call", who, kMsMaxStates);
+  *n_states = (int)states;
+  return LSLAM_OK;
+}
+
+int score_lattice_launch(lslam_map* map, const float* d_pts, int n, const float* centre_world, const int32_t* counts,
+                         const float* steps, int level, int n_states, float* d_volume, int* d_best_index, float* d_best_lik) {
+  lslam_context* ctx = map->ctx;
+  int rc = flush_pending(map);
+  if (rc) return rc;
+  MsJob J = score_job(map, level, kMsLattice, n_states);
+  J.first = 0; J.n = n;
+  J.c0 = centre_world[0]; J.c1 = centre_world[1]; J.c2 = centre_world[2];
+  J.d0 = steps[0]; J.d1 = steps[1]; J.d2 = steps[2];
+  J.nx = counts[0]; J.ny = counts[1]; J.nt = counts[2];
+  J.out_lik = d_volume;
+  rc = score_launch(map, J, d_pts);
+  if (rc || (!d_best_index && !d_best_lik)) return rc;
+  launch(ctx, "ms_best", k_ms_best, dim3(1), dim3(1024), 0, (const float*)d_volume, n_states, d_best_index, d_best_lik);
+  LSLAM_HIP(ctx, hipGetLastError());
+  return LSLAM_OK;
+}
+}  // namespace
+
+int lslam_map_score_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev, const int32_t* n_points,
+                              const int32_t* entry_container, const float* poses_world_dev, int level, float* out_residual_dev,
+                              float* out_likelihood_dev) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  size_t total = 0;
+  int rc = score_check(map, "lslam_map_score_batch_dev", n_entries, 1, n_containers, points_xy_dev, n_points, entry_container,
+                       poses_world_dev, out_likelihood_dev, level, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(map->ctx, hipSetDevice(map->ctx->device));
+  return score_batch_launch(map, n_entries, n_containers, points_xy_dev, n_points, entry_container, poses_world_dev, level,
+                            out_residual_dev, out_likelihood_dev);
+}
+
+int lslam_map_score_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                          const int32_t* entry_container, const float* poses_world, int level, float* out_residual,
+                          float* out_likelihood) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  size_t total = 0;
+  int rc = score_check(map, "lslam_map_score_batch", n_entries, 1, n_containers, points_xy, n_points, entry_container, poses_world,
+                       out_likelihood, level, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  rc = stage_points(map, points_xy, (int)total);  // -> d_pts (a staging buffer of the updates; not the cached container)
+  if (rc) return rc;
+  const size_t B = (size_t)n_entries;
+  LSLAM_HIP(ctx, map->d_score_io.reserve(5 * B));
+  float* d_poses = map->d_score_io.p;
+  float* d_res = d_poses + 3 * B;
+  float* d_lik = d_res + B;
+  LSLAM_HIP(ctx, hipMemcpyAsync(d_poses, poses_world, 3 * B * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  rc = score_batch_launch(map, n_entries, n_containers, map->d_pts.p, n_points, entry_container, d_poses, level, d_res, d_lik);
+  if (rc) return rc;
+  if (out_residual) LSLAM_HIP(ctx, hipMemcpyAsync(out_residual, d_res, B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipMemcpyAsync(out_likelihood, d_lik, B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // one wait for the whole batch
+  return LSLAM_OK;
+}
+
+int lslam_map_pose_covariance_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev,
+                                        const int32_t* n_points, const int32_t* entry_container, const float* poses_world_dev,
+                                        int level, float* out_likelihoods_dev, float* out_cov_map_dev, float* out_cov_world_dev) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  size_t total = 0;
+  int rc = score_check(map, "lslam_map_pose_covariance_batch_dev", n_entries, 7, n_containers, points_xy_dev, n_points,
+                       entry_container, poses_world_dev, out_likelihoods_dev, level, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(map->ctx, hipSetDevice(map->ctx->device));
+  return score_cov_launch(map, n_entries, n_containers, points_xy_dev, n_points, entry_container, poses_world_dev, level,
+                          out_likelihoods_dev, out_cov_map_dev, out_cov_world_dev);
+}
+
+int lslam_map_pose_covariance_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                                    const int32_t* entry_container, const float* poses_world, int level, float* out_likelihoods,
+                                    float* out_cov_map, float* out_cov_world) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  size_t total = 0;
+  int rc = score_check(map, "lslam_map_pose_covariance_batch", n_entries, 7, n_containers, points_xy, n_points, entry_container,
+                       poses_world, out_likelihoods, level, &total);
+  if (rc || n_entries == 0) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  rc = stage_points(map, points_xy, (int)total);
+  if (rc) return rc;
+  const size_t B = (size_t)n_entries;
+  LSLAM_HIP(ctx, map->d_score_io.reserve(28 * B));
+  float* d_poses = map->d_score_io.p;
+  float* d_lik = d_poses + 3 * B;
+  float* d_cm = d_lik + 7 * B;
+  float* d_cw = d_cm + 9 * B;
+  LSLAM_HIP(ctx, hipMemcpyAsync(d_poses, poses_world, 3 * B * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  rc = score_cov_launch(map, n_entries, n_containers, map->d_pts.p, n_points, entry_container, d_poses, level, d_lik,
+                        out_cov_map ? d_cm : (float*)nullptr, out_cov_world ? d_cw : (float*)nullptr);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipMemcpyAsync(out_likelihoods, d_lik, 7 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_cov_map) LSLAM_HIP(ctx, hipMemcpyAsync(out_cov_map, d_cm, 9 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_cov_world) LSLAM_HIP(ctx, hipMemcpyAsync(out_cov_world, d_cw, 9 * B * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LSLAM_OK;
+}
+
+int lslam_map_score_lattice_dev(lslam_map* map, const float* points_xy_dev, int n, const float centre_world[3],
+                                const int32_t counts[3], const float steps[3], int level, float* out_volume_dev,
+                                int32_t* out_best_index_dev, float* out_best_likelihood_dev) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  int n_states = 0;
+  int rc = score_lattice_check(map, "lslam_map_score_lattice_dev", points_xy_dev, n, centre_world, counts, steps, level,
+                               out_volume_dev, &n_states);
+  if (rc) return rc;
+  LSLAM_HIP(map->ctx, hipSetDevice(map->ctx->device));
+  return score_lattice_launch(map, points_xy_dev, n, centre_world, counts, steps, level, n_states, out_volume_dev,
+                              out_best_index_dev, out_best_likelihood_dev);
+}
+
+int lslam_map_score_lattice(lslam_map* map, const float* points_xy, int n, const float centre_world[3], const int32_t counts[3],
+                            const float steps[3], int level, float* out_volume, int32_t* out_best_index,
+                            float* out_best_likelihood) {
+  if (!map) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  int n_states = 0;
+  int rc = score_lattice_check(map, "lslam_map_score_lattice", points_xy, n, centre_world, counts, steps, level, out_volume, &n_states);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  rc = stage_points(map, points_xy, n);
+  if (rc) return rc;
+  const size_t N = (size_t)n_states;
+  LSLAM_HIP(ctx, map->d_score_io.reserve(N + 2));
+  float* d_vol = map->d_score_io.p;
+  int* d_bi = reinterpret_cast<int*>(d_vol + N);
+  float* d_bl = d_vol + N + 1;
+  rc = score_lattice_launch(map, map->d_pts.p, n, centre_world, counts, steps, level, n_states, d_vol, d_bi, d_bl);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipMemcpyAsync(out_volume, d_vol, N * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_best_index) LSLAM_HIP(ctx, hipMemcpyAsync(out_best_index, d_bi, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_best_likelihood) LSLAM_HIP(ctx, hipMemcpyAsync(out_best_likelihood, d_bl, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LSLAM_OK;
 }
 

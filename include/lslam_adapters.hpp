@@ -406,6 +406,36 @@ class MapRepGpu {
                                    outCovs);
     if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
   }
+  // float getLikelihoodForState(state, dataPoints) (H/map/OccGridMapUtil.h:342-347) for many states at once: entry e =
+  // (container entryContainer[e], WORLD pose statesWorld[e]) on `level` of the map as it is.  outResiduals
+  // (getResidualForState, :357-374) may be nullptr.  Containers as for matchDataBatch.  A pure query.
+  void getLikelihoodForStates(int nEntries, const float* statesWorld, int nContainers, const float* pointsXY,
+                              const int32_t* nPoints, const int32_t* entryContainer, int level, float* outLikelihoods,
+                              float* outResiduals = nullptr) {
+    int rc = lslam_map_score_batch(h_, nEntries, nContainers, pointsXY, nPoints, entryContainer, statesWorld, level, outResiduals,
+                                   outLikelihoods);
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  // Eigen::Matrix3f getCovarianceForPose(mapPose, dataPoints) (:249-306) and getCovMatrixWorldCoords (:314-339) for many
+  // poses at once (WORLD poses; the sigma points are taken on the level's raster): outLikelihoods[nEntries][7],
+  // outCovMap / outCovWorld [nEntries][9] row-major, either may be nullptr.
+  void getCovarianceForPoses(int nEntries, const float* posesWorld, int nContainers, const float* pointsXY, const int32_t* nPoints,
+                             const int32_t* entryContainer, int level, float* outLikelihoods, float* outCovMap,
+                             float* outCovWorld) {
+    int rc = lslam_map_pose_covariance_batch(h_, nEntries, nContainers, pointsXY, nPoints, entryContainer, posesWorld, level,
+                                             outLikelihoods, outCovMap, outCovWorld);
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  // getLikelihoodForState over the lattice centreWorld + (i - nx/2, j - ny/2, k - nt/2) * steps of one container:
+  // outVolume[nt][ny][nx]; returns the best state's linear index (-1: every likelihood is NaN), its likelihood in
+  // *outBestLikelihood when given.
+  int scoreLattice(const float* pointsXY, int n, const float centreWorld[3], const int32_t counts[3], const float steps[3],
+                   int level, float* outVolume, float* outBestLikelihood = nullptr) {
+    int32_t best = -1;
+    int rc = lslam_map_score_lattice(h_, pointsXY, n, centreWorld, counts, steps, level, outVolume, &best, outBestLikelihood);
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+    return best;
+  }
   // getGridMap(level) contents: log-odds plane / the int8 data of nav_msgs::OccupancyGrid
   void readLogOdds(int level, float* out) { lslam_map_read_logodds(h_, level, out); }
   void readOccupancy(int level, int8_t* out) { lslam_map_read_occupancy_i8(h_, level, out); }

@@ -682,6 +682,57 @@ int lslam_map_match_batch_dev(lslam_map* map, int n_entries, int n_containers, c
  * within 1e-5 of the reference's poses on the test sequences, tolerance 1e-4 m / 1e-4 rad.  LSLAM_MAP_OPT_ORDERED_SUMS = 1
  * selects the kernel that adds them in point order like the reference's sequential loop (H/matcher/ScanMatcher.h:94-126)
  * and evaluates the libm calls in double like its host code: bit-equal to the CPU restatement, ~4x slower. */
+/* POSE SCORING: how well does a container fit ONE level of the map at a pose?  The half of OccGridMapUtil the matcher does
+ * not use (H/map/OccGridMapUtil.h): what tells the K answers of lslam_map_match_batch apart, and -- as a lattice -- what
+ * finds the start pose the local Gauss-Newton matcher needs.
+ * Common to the three calls: containers as for lslam_map_match_batch (points_xy back to back in level-0 map-cell units,
+ * n_points[n_containers], entry_container[n_entries] or NULL, at most 65536 points each, in BOTH sum modes); poses are WORLD
+ * poses and go to the level's raster as the matcher's do (getMapCoordsPose, GridMapBase.h:238-242), points are scaled by
+ * 2^-level (DataContainer::setFrom, MapRepMultiMap.h:161); `level` is per call.  A point outside pointOutOfMapBounds
+ * contributes the value 0; an empty container has residual 0 and likelihood 0 / 0 = NaN, as the reference's arithmetic gives.
+ * Default: fp32 tree sums, hardware exp / rcp; a state's result depends on its container, its pose and the map only -- not on
+ * the batch around it or on the call it came through.  LSLAM_MAP_OPT_ORDERED_SUMS = 1: the residual is added in container
+ * order with exp / sin / cos in double, bit for bit the reference's result.  (LSLAM_SCORE_CHUNK = 2 | 4 | 8 in the environment
+ * when a map is created: points per lane in flight in the default kernel, for measurements; results do not depend on it.)
+ * PURE QUERIES: no plane, no cached container, no lslam_map_cached_points changes; like every reader they enqueue a pending
+ * pipelined apply first.  n_entries == 0 is LSLAM_OK and launches nothing.  LSLAM_ERR_INVALID_ARGUMENT, outputs untouched: a
+ * level outside the pyramid, a container index out of range, a lattice with a non-positive count, missing arrays.
+ * The host forms return with the results in the caller's arrays; the _dev forms take points, poses and outputs in HBM
+ * (n_points / entry_container / centre / counts / steps stay host arrays) and are ASYNCHRONOUS on lslam_stream().
+ *
+ * lslam_map_score_batch: getResidualForState (:357-374, interpMapValue :379-434) and getLikelihoodForState /
+ * getLikelihoodForResidual (:342-355) for n_entries (container, pose) pairs -> out_residual[n_entries] (may be NULL),
+ * out_likelihood[n_entries] = 1 - residual / n. */
+int lslam_map_score_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                          const int32_t* entry_container, const float* poses_world, int level, float* out_residual,
+                          float* out_likelihood);
+int lslam_map_score_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev, const int32_t* n_points,
+                              const int32_t* entry_container, const float* poses_world_dev, int level, float* out_residual_dev,
+                              float* out_likelihood_dev);
+/* getCovarianceForPose (:249-306) and getCovMatrixWorldCoords (:314-339) per entry: the likelihoods of the seven sigma points
+ * (+-1.5 cells in x, +-1.5 cells in y, +-0.05 rad, then the pose itself, on the level's raster) ->
+ * out_likelihoods[n_entries][7]; their likelihood-weighted covariance -> out_cov_map[n_entries][9] (row-major 3 x 3, level
+ * cells / rad) and, scaled with the level's cell length, out_cov_world[n_entries][9] (m / rad); either cov array may be NULL.
+ * The covariance is computed on the device behind the scoring launch, in fp32 and in Eigen's expression order. */
+int lslam_map_pose_covariance_batch(lslam_map* map, int n_entries, int n_containers, const float* points_xy, const int32_t* n_points,
+                                    const int32_t* entry_container, const float* poses_world, int level, float* out_likelihoods,
+                                    float* out_cov_map, float* out_cov_world);
+int lslam_map_pose_covariance_batch_dev(lslam_map* map, int n_entries, int n_containers, const float* points_xy_dev,
+                                        const int32_t* n_points, const int32_t* entry_container, const float* poses_world_dev,
+                                        int level, float* out_likelihoods_dev, float* out_cov_map_dev, float* out_cov_world_dev);
+/* getLikelihoodForState (:342-347) over a lattice of poses around centre_world, for one container of n points: state (i, j, k),
+ * i < counts[0] = nx, j < counts[1] = ny, k < counts[2] = nt, has the world pose
+ *   (c.x + (float)(i - nx/2) * steps[0],  c.y + (float)(j - ny/2) * steps[1],  c.theta + (float)(k - nt/2) * steps[2])
+ * (integer division, fp32, product and sum rounded separately), evaluated on the device: no pose array goes up.
+ * out_volume[nt][ny][nx]: the likelihoods, bit-identical to lslam_map_score_batch called with these poses.
+ * out_best_index / out_best_likelihood (each may be NULL): the state with the highest likelihood, the lowest linear index
+ * (k * ny + j) * nx + i among equals; -1 and NaN when every likelihood is NaN.  At most 2^24 states per call. */
+int lslam_map_score_lattice(lslam_map* map, const float* points_xy, int n, const float centre_world[3], const int32_t counts[3],
+                            const float steps[3], int level, float* out_volume, int32_t* out_best_index,
+                            float* out_best_likelihood);
+int lslam_map_score_lattice_dev(lslam_map* map, const float* points_xy_dev, int n, const float centre_world[3],
+                                const int32_t counts[3], const float steps[3], int level, float* out_volume_dev,
+                                int32_t* out_best_index_dev, float* out_best_likelihood_dev);
 /* The batched update's scratch (lslam_map_update_batch*): every scan of a batch owns a WINDOW of 8x8-cell tiles -- the
  * square its rays can reach from its begin cell -- in a pool of 64-byte tile slots, not a byte plane of the whole map
  * (a 1081-beam scan with 20 m of range on a 0.025 m map: 2.6 MB, whatever the map's size).
