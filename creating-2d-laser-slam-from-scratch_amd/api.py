@@ -532,6 +532,8 @@ def lib() -> C.CDLL:
     L.lslam_matcher_lone_kernel_launches.restype = C.c_int64
     L.lslam_matcher_rows_mfma_launches.argtypes = [vp]
     L.lslam_matcher_rows_mfma_launches.restype = C.c_int64
+    L.lslam_matcher_fine_mfma_launches.argtypes = [vp]
+    L.lslam_matcher_fine_mfma_launches.restype = C.c_int64
     L.lslam_matcher_coarse_form_launches.argtypes = [vp, vp]
     i64 = C.c_int64
     L.lslam_scan_cache_create.argtypes = [vp, C.POINTER(LaserParams), C.POINTER(vp)]
@@ -674,7 +676,7 @@ class Context:
 
 MATCHER_OPTIONS = {"row_occupancy": 1, "collect_stats": 2, "lds_staged": 3, "pipeline_depth": 4, "step_kernel": 5,
                    "step_min_scans": 6, "rows_waves": 7, "check_output_reuse": 8, "lone_kernel": 9,
-                   "rows_mfma": 10}  # LSLAM_OPT_*
+                   "rows_mfma": 10, "fine_mfma": 11}  # LSLAM_OPT_*
 # LSLAM_FORM_* in the header's order
 COARSE_FORMS = ("generic", "rows_linear", "rows_tiled", "rows_multiwave", "rows_lds_staged", "rows_stats_linear",
                 "rows_stats_tiled", "rows_stats_lds_staged", "big", "fine_rows", "fine_tile3")
@@ -773,6 +775,12 @@ class ScanMatcher:
         """Row-kernel launches that summed their rows with the i8 MFMA (set_option('rows_mfma', 1) and a grid whose bytes
         are all <= 127) so far; they are counted in coarse_form_launches() under the same form names as the packed form."""
         return int(self.L.lslam_matcher_rows_mfma_launches(self.h))
+
+    @property
+    def fine_mfma_launches(self) -> int:
+        """k_resp_tile3 launches that summed their patches with the i8 MFMA (set_option('fine_mfma', 1) and a grid whose
+        bytes are all <= 127) so far; coarse_form_launches() counts them under fine_tile3 like the packed form's."""
+        return int(self.L.lslam_matcher_fine_mfma_launches(self.h))
 
     def coarse_form_launches(self) -> dict:
         """Response-kernel launches so far, per form (lslam_matcher_coarse_form_launches): every coarse form goes out

@@ -16,7 +16,8 @@
 //   k_reduce_coarse  S blocks      penalties, max, tie average, positional covariance; then the fine
 //                                  lattice of the scan
 //   k_resp_tile3     S*nA/3 waves  fine pass: one 12-byte load per (beam, angle) from overlapping 4x4 blocks
-//                                  (k_tile4), three angles per wave from 1536 scans up (one below);
+//                                  (k_tile4), three angles per wave from 1536 scans up (one below), the
+//                                  patch bytes summed with the i8 MFMA (LSLAM_OPT_FINE_MFMA);
 //                                  k_resp_rows<1,4> for small batches
 //   k_reduce_fine    S blocks      same reductions + angular covariance (Mapper.cpp:431-506, 535-692)
 //   k_resp_generic                 the same sums for arbitrary lattices; as block_generic_fallback it
@@ -513,6 +514,16 @@ __device__ __forceinline__ void wsync() {
 // the epilogue adds its four registers and the four 16-lane rows, and lane n < nx stores candidate n.  The bytes are read as
 // SIGNED: the host takes this form only for grids whose bytes are all <= 127 (every grid the library builds is <= 100).
 typedef int v4i_t __attribute__((ext_vector_type(4)));
+// The column sums of such an accumulator over the whole wave: the four registers in the lane (rows 4 (l >> 4) + 0..3 of D),
+// then the four 16-lane rows with the two row swaps (v_permlane32_swap, v_permlane16_swap: x[l] + x[l ^ 32], then
+// + x[l ^ 16]); every lane then holds column l & 15.  No LDS.
+__device__ __forceinline__ uint32_t wave_cols_sum(const v4i_t d) {
+  uint32_t v = (uint32_t)((d[0] + d[1]) + (d[2] + d[3]));
+  const auto h = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  v = h[0] + h[1];
+  const auto q = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  return q[0] + q[1];
+}
 template <int NXD, int NYC, bool TILED, bool STATS, bool LDSB, bool SOLO, bool OUT_LDS = !SOLO, bool MFMA = false>
 __device__ __forceinline__ void resp_rows_wave(
     const int s, const int a, const int slice, const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int step,
@@ -1030,16 +1041,11 @@ __device__ __forceinline__ void resp_rows_wave(
     }
 
     if constexpr (MFMA) {
-      // Reduce over the wave: the accumulator's four registers in the lane (rows 4 (l >> 4) + 0..3 of D), then the four
-      // 16-lane rows with the two row swaps (v_permlane32_swap, v_permlane16_swap: x[l] + x[l ^ 32], then + x[l ^ 16]);
-      // every lane then holds candidate l & 15 of lattice row j, and lanes 0 .. nx - 1 store it.  No LDS.
+      // Reduce over the wave (wave_cols_sum): every lane then holds candidate l & 15 of lattice row j, and lanes
+      // 0 .. nx - 1 store it.  No LDS.
 #pragma unroll
       for (int j = 0; j < NYC; j++) {
-        uint32_t v = (uint32_t)((macc[j][0] + macc[j][1]) + (macc[j][2] + macc[j][3]));
-        const auto h = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-        v = h[0] + h[1];
-        const auto q = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        v = q[0] + q[1];
+        const uint32_t v = wave_cols_sum(macc[j]);
         if (lane < pc.nx && j0 + j < pc.ny) {
           if constexpr (OUT_LDS) {
             lds_out[a * ncand + (j0 + j) * pc.nx + lane] = (int32_t)v;
@@ -1209,13 +1215,37 @@ k_tile4(const uint8_t* __restrict__ grid, int stride, int data_size, uint4* __re
 // gather unit 85 % busy; the coalesced 16-byte-per-lane point load is charged about as much as the block gather): the
 // angles share the point load, and their block gathers are independent loads in flight together.  Measured per 4096-scan launch: 1 angle per wave
 // 119 us, 2: 96, 3: 92, 4: 95; below ~1000 scans one angle per wave (more waves) is the faster form (256 scans: 14 vs 22 us).
+// (Those four figures are the PACKED form's: five packed accumulators and three selectors per angle.)
+// The MFMA form (LSLAM_OPT_FINE_MFMA) was measured again, since it keeps four accumulator registers per angle and no
+// selectors, and computes nothing for a group's angles past the last (11 angles: 3 + 3 + 3 + 2 against 4 + 4 + 3): three
+// angles per wave 72.3 +- 0.9 us per 4096-scan launch (45 VGPRs + 12 AGPRs, 8 waves per SIMD), four 71.8 +- 0.8 us
+// (57 + 16, 6 waves per SIMD) -- inside each other's launch-to-launch spread, so it stays at three and keeps the residency
+// (profiles/r10/README.md; the packed form on the same day: 83.5 +- 0.9 us).
 #if !defined(LSLAM_TUNE_TILE3_MIN)
 #define LSLAM_TUNE_TILE3_MIN 1536
 #endif
 constexpr int kTile3ManyAngles = 3, kTile3ManyMinScans = LSLAM_TUNE_TILE3_MIN;
+#if !defined(LSLAM_TUNE_TILE3_MFMA_ANGLES)
+#define LSLAM_TUNE_TILE3_MFMA_ANGLES 3
+#endif
+constexpr int kTile3MfmaAngles = LSLAM_TUNE_TILE3_MFMA_ANGLES;  // angles per wave of the MFMA form in the same batches
+template <int N, class F>
+__device__ __forceinline__ void with_count(const int n, F&& f) {  // f(integral_constant<n>) for a wave-uniform n in 1..N
+  if (n == N) f(std::integral_constant<int, N>{});
+  else if constexpr (N > 1) with_count<N - 1>(n, f);
+}
 // One wave64: the 9 numerators of each of the angles a0 .. a0 + kTile3Angles - 1 of scan s, written to r_scan[a * 9 + c]
 // (r_scan = the scan's numerators: resp + s * resp_stride in k_resp_tile3, the block's LDS copy in k_match_step).
-template <int kTile3Angles>
+//
+// MFMA = true (LSLAM_OPT_FINE_MFMA, k_resp_tile3 only): the patch bytes are summed on the matrix pipe, as in phase B of
+// resp_rows_wave.  Row j of a beam's patch, shifted right by 8 dx bits, is dword j of the A operand of
+// v_mfma_i32_16x16x64_i8 (candidate (i, j) = byte 4 j + i; bytes 3, 7, 11 hold a neighbouring column and bytes 12..15 zero:
+// output columns nobody stores), B is the same per-lane one-hot, and C is one int32x4 accumulator per angle, carried over
+// the blocks of beams.  The instruction is issued with the whole wave converged: the beam loop has a wave-uniform trip count,
+// and a lane past the last beam, a NaN point and a block outside the grid all read the zero block at offset 0 instead of
+// branching.  A group's angles beyond pc.na do not exist in this form: the body is instantiated for the number of angles the
+// wave really has (a wave-uniform choice).  The epilogue is wave_cols_sum per angle; no DPP sums, no v_readlane.
+template <int kTile3Angles, bool MFMA = false>
 __device__ __forceinline__ void resp_tile3_wave(const int s, const int a0, const int lane, const uint4* __restrict__ tiles,
                                                 int tile_cols, const Geom& g, const PassCfg& pc,
                                                 const Lattice* __restrict__ lat, const double2* __restrict__ cossin,
@@ -1286,6 +1316,46 @@ __device__ __forceinline__ void resp_tile3_wave(const int s, const int a0, const
     dx = (uint32_t)x & 1u;
     return ok;
   };
+  if constexpr (MFMA) {
+    with_count<kTile3Angles>(min(kTile3Angles, pc.na - a0), [&](auto n_angles) {
+      constexpr int N = decltype(n_angles)::value;
+      const uint32_t hot = 1u << ((lane & 3) * 8), hq = ((uint32_t)lane >> 2) & 3u;
+      const v4i_t B{(int)(hq == 0u ? hot : 0u), (int)(hq == 1u ? hot : 0u), (int)(hq == 2u ? hot : 0u), (int)(hq == 3u ? hot : 0u)};
+      v4i_t macc[N];
+#pragma unroll
+      for (int q = 0; q < N; q++) macc[q] = v4i_t{0, 0, 0, 0};
+      const int trips = (g.n_beams + 63) >> 6;  // wave-uniform: every lane issues every MFMA
+      double2 p = lp[min(lane, g.n_beams - 1)];
+      for (int t = 0, b = lane; t < trips; t++, b += 64) {
+        const double2 pn = lp[min(b + 64, g.n_beams - 1)];  // next point in flight while this one is used
+        // a lane without a beam (past the end, NaN = INVALID_SCAN) works on the point (0, 0) -- the fp32 estimate decides
+        // it, so `p` itself is not read -- and gathers the zero block
+        const bool valid = (int)(b < g.n_beams) & (int)!isnan(p.x);
+        const float x32 = valid ? (float)p.x : 0.0f, y32 = valid ? (float)p.y : 0.0f;
+        uint32_t off[N], dx[N], rr[N][3];
+#pragma unroll
+        for (int q = 0; q < N; q++) {
+          const bool ok = block_of(p, x32, y32, q, off[q], dx[q]) && valid;
+          off[q] = ok ? off[q] : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < N; q++) __builtin_memcpy(rr[q], __builtin_assume_aligned((const uint8_t*)tiles + off[q], 4), 12);
+#pragma unroll
+        for (int q = 0; q < N; q++) {
+          const uint32_t sh = dx[q] * 8u;
+          const v4i_t A{(int)(rr[q][0] >> sh), (int)(rr[q][1] >> sh), (int)(rr[q][2] >> sh), 0};
+          macc[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, macc[q], 0, 0, 0);
+        }
+        p = pn;
+      }
+#pragma unroll
+      for (int q = 0; q < N; q++) {
+        const uint32_t v = wave_cols_sum(macc[q]);  // every lane: column lane & 15 = candidate (i, j) at 4 j + i
+        if (lane < 12 && (lane & 3) != 3) r_scan[(a0 + q) * 9 + (lane >> 2) * 3 + (lane & 3)] = (int32_t)v;
+      }
+    });
+    return;
+  }
   double2 p = lp[min(lane, g.n_beams - 1)];
   for (int b = lane; b < g.n_beams; b += 64) {
     const double2 pn = lp[min(b + 64, g.n_beams - 1)];  // next point in flight while this one is used
@@ -1328,7 +1398,7 @@ __device__ __forceinline__ void resp_tile3_wave(const int s, const int a0, const
   }
 }
 
-template <int kTile3Angles>
+template <int kTile3Angles, bool MFMA = false>
 __global__ void __launch_bounds__(64)
 k_resp_tile3(const uint4* __restrict__ tiles, int tile_cols, Geom g, PassCfg pc, const Lattice* __restrict__ lat,
              const double2* __restrict__ cossin, const double2* __restrict__ local, int32_t* __restrict__ resp, size_t resp_stride, int S) {
@@ -1338,7 +1408,8 @@ k_resp_tile3(const uint4* __restrict__ tiles, int tile_cols, Geom g, PassCfg pc,
   const int s = (r / pairs) * 8 + xcd;  // all angles of a scan on one XCD, like k_resp_rows
   const int a0 = (r % pairs) * kTile3Angles;
   if (s >= S) return;
-  resp_tile3_wave<kTile3Angles>(s, a0, (int)threadIdx.x, tiles, tile_cols, g, pc, lat, cossin, local, resp + (size_t)s * resp_stride);
+  resp_tile3_wave<kTile3Angles, MFMA>(s, a0, (int)threadIdx.x, tiles, tile_cols, g, pc, lat, cossin, local,
+                                      resp + (size_t)s * resp_stride);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3699,6 +3770,8 @@ struct lslam_matcher {
   // checked on the host copy by lslam_matcher_set_grid_u8, false after lslam_matcher_set_grid_u8_dev (bytes unseen)
   bool grid_fits_i8 = true;
   int64_t rows_mfma_launches = 0;   // coarse / fine row launches that took the MFMA accumulate (lslam_matcher_rows_mfma_launches)
+  bool fine_mfma = true;            // lslam_matcher_set_option(LSLAM_OPT_FINE_MFMA): k_resp_tile3 sums the patch bytes on the matrix pipe (same eligibility)
+  int64_t fine_mfma_launches = 0;   // k_resp_tile3 launches that did (lslam_matcher_fine_mfma_launches)
   // the streaming front-end's speculative anchor chain (anchor_spec_block): asked for before a match, reported after it
   SpecArgs spec_req{};
   bool spec_armed = false, spec_launched = false;
@@ -4071,12 +4144,22 @@ int match_batch_impl(lslam_matcher* m, int S, const RT* d_ranges, int stride, co
 #define LSLAM_TILE3_ARGS                                                                                                \
   (const uint4*)m->d_tiles, m->tile_cols, g, p, (const Lattice*)m->d_lat.p, (const double2*)m->d_cossin.p,              \
       (const double2*)m->d_local.p, m->d_resp.p, resp_stride, S
-      if (S >= kTile3ManyMinScans)
-        launch(ctx, "resp_tile_fine", k_resp_tile3<kTile3ManyAngles>,
-               dim3((unsigned)((long long)((S + 7) / 8) * 8 * ((p.na + kTile3ManyAngles - 1) / kTile3ManyAngles))), dim3(64), 0,
+      // the MFMA sums (LSLAM_OPT_FINE_MFMA) read the blocks' bytes signed, like LSLAM_OPT_ROWS_MFMA: same eligibility
+      const bool fine_mfma = m->fine_mfma && m->grid_fits_i8;
+      auto groups_grid = [&](int angles) {
+        return dim3((unsigned)((long long)((S + 7) / 8) * 8 * ((p.na + angles - 1) / angles)));
+      };
+      if (S >= kTile3ManyMinScans && fine_mfma)
+        launch(ctx, "resp_tile_fine", k_resp_tile3<kTile3MfmaAngles, true>, groups_grid(kTile3MfmaAngles), dim3(64), 0,
                LSLAM_TILE3_ARGS);
+      else if (S >= kTile3ManyMinScans)
+        launch(ctx, "resp_tile_fine", k_resp_tile3<kTile3ManyAngles>, groups_grid(kTile3ManyAngles), dim3(64), 0,
+               LSLAM_TILE3_ARGS);
+      else if (fine_mfma)
+        launch(ctx, "resp_tile_fine", k_resp_tile3<1, true>, dim3((unsigned)waves), dim3(64), 0, LSLAM_TILE3_ARGS);
       else
         launch(ctx, "resp_tile_fine", k_resp_tile3<1>, dim3((unsigned)waves), dim3(64), 0, LSLAM_TILE3_ARGS);
+      if (fine_mfma) m->fine_mfma_launches++;
 #undef LSLAM_TILE3_ARGS
     } else if (variant) {
       // small batches: split the beams of one (scan, angle) over several waves to fill the chip
@@ -4998,6 +5081,9 @@ int lslam_matcher_set_option(lslam_matcher* m, int option, int value) {
     case LSLAM_OPT_ROWS_MFMA:
       m->rows_mfma = value != 0;
       return LSLAM_OK;
+    case LSLAM_OPT_FINE_MFMA:
+      m->fine_mfma = value != 0;
+      return LSLAM_OK;
     case LSLAM_OPT_STEP_MIN_SCANS: {
       if (value < 1) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "step kernel: minimum batch %d < 1", value);
       m->step_min_scans = value;
@@ -5028,6 +5114,7 @@ int lslam_matcher_get_option(const lslam_matcher* m, int option) {
     case LSLAM_OPT_STEP_MIN_SCANS: return m->step_min_scans;
     case LSLAM_OPT_ROWS_WAVES: return m->rows_waves;
     case LSLAM_OPT_ROWS_MFMA: return m->rows_mfma ? 1 : 0;
+    case LSLAM_OPT_FINE_MFMA: return m->fine_mfma ? 1 : 0;
     case LSLAM_OPT_CHECK_OUTPUT_REUSE: return m->check_out_reuse ? 1 : 0;
     case LSLAM_OPT_LONE_KERNEL: return m->lone_waves + (m->lone_waves && m->lone_one_task_wave ? 100 : 0);
     default: return LSLAM_ERR_INVALID_ARGUMENT;
@@ -5044,6 +5131,7 @@ int64_t lslam_matcher_pipelined_steps(const lslam_matcher* m) { return m ? (int6
 int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->step_launches : 0; }
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m) { return m ? (int64_t)m->lone_launches : 0; }
 int64_t lslam_matcher_rows_mfma_launches(const lslam_matcher* m) { return m ? m->rows_mfma_launches : 0; }
+int64_t lslam_matcher_fine_mfma_launches(const lslam_matcher* m) { return m ? m->fine_mfma_launches : 0; }
 int lslam_matcher_coarse_form_launches(const lslam_matcher* m, int64_t out[LSLAM_FORM_COUNT]) {
   if (!m || !out) return LSLAM_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < LSLAM_FORM_COUNT; i++) out[i] = m->form_launches[i];

@@ -210,9 +210,18 @@ void* lslam_matcher_grid_dev_ptr(lslam_matcher* m);
  *    numerators either way; the launches are counted under the same form names, and lslam_matcher_rows_mfma_launches
  *    counts those that took the MFMA accumulate.  The one-launch kernels (LSLAM_OPT_STEP_KERNEL / LSLAM_OPT_LONE_KERNEL),
  *    the LDS-staged experiment and rows of up to 4 positions keep the packed form. */
+/*  LSLAM_OPT_FINE_MFMA (default 1): the fine response kernel on the 4x4 blocks (k_resp_tile3, batches whose fine pass fills
+ *    the chip) sums the bytes of each beam's 3x3 patch with v_mfma_i32_16x16x64_i8 -- the three patch rows, shifted to the
+ *    patch's column, against the same one-hot operand, one int32x4 accumulator per angle -- instead of v_perm_b32 selections
+ *    into packed 16-bit fields and a DPP + v_readlane reduction per candidate.  A group's angles beyond the last fine angle
+ *    cost nothing in this form.  Signed bytes again: taken under exactly the conditions of LSLAM_OPT_ROWS_MFMA (every byte of
+ *    the grid <= 127 as far as the host knows), the packed form otherwise and for value 0.  Same numerators either way; the
+ *    launches stay under the form name fine_tile3 and the profile name resp_tile_fine, and
+ *    lslam_matcher_fine_mfma_launches counts those that summed on the matrix pipe.  The one-launch kernels keep the packed
+ *    form. */
 enum { LSLAM_OPT_ROW_OCCUPANCY = 1, LSLAM_OPT_COLLECT_STATS = 2, LSLAM_OPT_LDS_STAGED = 3, LSLAM_OPT_PIPELINE_DEPTH = 4,
        LSLAM_OPT_STEP_KERNEL = 5, LSLAM_OPT_STEP_MIN_SCANS = 6, LSLAM_OPT_ROWS_WAVES = 7, LSLAM_OPT_CHECK_OUTPUT_REUSE = 8, LSLAM_OPT_LONE_KERNEL = 9,
-       LSLAM_OPT_ROWS_MFMA = 10 };
+       LSLAM_OPT_ROWS_MFMA = 10, LSLAM_OPT_FINE_MFMA = 11 };
 /* current value of an option (negative: error code) */
 int lslam_matcher_get_option(const lslam_matcher* m, int option);
 /* Order the context stream behind every pipelined step in flight (no host wait).  No-op at depth 1. */
@@ -225,6 +234,8 @@ int64_t lslam_matcher_step_kernel_launches(const lslam_matcher* m);
 int64_t lslam_matcher_lone_kernel_launches(const lslam_matcher* m);
 /* diagnostics: k_resp_rows / k_resp_rows_mw launches that took the MFMA accumulate (LSLAM_OPT_ROWS_MFMA) so far */
 int64_t lslam_matcher_rows_mfma_launches(const lslam_matcher* m);
+/* diagnostics: k_resp_tile3 launches that summed on the matrix pipe (LSLAM_OPT_FINE_MFMA) so far */
+int64_t lslam_matcher_fine_mfma_launches(const lslam_matcher* m);
 /* diagnostics: which FORM of the response kernel took the passes of the matches so far.  Every coarse form goes out under
  * the same profile name (resp_rows_coarse), and the dispatch falls back silently (a batch below the tiled planes' threshold,
  * more than 2048 beams, planes that could not be allocated ...): a test or an A/B run that selects a form with

@@ -46,7 +46,13 @@ def main(pmc_path, scans):
              "A_cell+A_emit+A_estimate+A_point+A_loop:1080,B_drain:1016,epilogue:283,parked:50,other:51")]
     t0 = line_of(src, "__device__ __forceinline__ void resp_tile3_wave(")
     t1 = line_of(src, "k_resp_tile3(const uint4* __restrict__ tiles", t0)
-    jobs.append(("resp_tile_fine", "k_resp_tile3<3>", "k_resp_tile3ILi3E", f"all:{t0}-{t1}", "all+other:1"))
+    # the fine kernel in the form the counter pass ran: <3, MFMA = true> by default (its static mix is taken over the bodies for
+    # 3, 2 and 1 angles alike), <3, false> = the packed form with set_option("fine_mfma", 0); a pass before round 10 names "<3>"
+    for pmc_prefix, mangled in (("k_resp_tile3<3, true>", "k_resp_tile3ILi3ELb1E"), ("k_resp_tile3<3, false>", "k_resp_tile3ILi3ELb0E"),
+                                ("k_resp_tile3<3>", "k_resp_tile3ILi3ELb0E")):
+        if any(k.startswith(pmc_prefix) for k in pmc):
+            jobs.append(("resp_tile_fine", pmc_prefix, mangled, f"all:{t0}-{t1}", "all+other:1"))
+            break
     for short, pmc_prefix, mangled, ph, dyn in jobs:
         c = next((v for k, v in pmc.items() if k.startswith(pmc_prefix)), None)
         if not c or not c.get("GRBM_GUI_ACTIVE") or not c.get("SQ_WAVES"):
