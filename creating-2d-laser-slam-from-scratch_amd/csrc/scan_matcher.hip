@@ -3173,6 +3173,17 @@ __device__ __forceinline__ void mark_reachable(int n, int first, int* ja, int* j
   }
 }
 
+// ROI cell of a base point (AddScan, Mapper.cpp:723-729): false where the point sets no cell -- outside the ROI (IsUpTo), or
+// a non-finite coordinate.  FindValidPoints keeps whole runs, so NaN and +-inf points inside a kept run (and the NaN points in
+// front of a kept first run) do reach AddScan; on the host (int)Round(NaN) and (int)Round(+-inf) are all INT_MIN, which fails
+// IsUpTo, while the device's conversion turns NaN into 0 -- ROI cell 0, a footprint in the grid's corner.
+__device__ __forceinline__ bool base_point_cell(double2 q, const Geom& g, int& gx, int& gy) {
+  if (!isfinite(q.x) || !isfinite(q.y)) return false;
+  gx = world_to_grid(q.x, g.off_x, g.scale);
+  gy = world_to_grid(q.y, g.off_y, g.scale);
+  return gx >= 0 && gx < g.roi_w && gy >= 0 && gy < g.roi_h;
+}
+
 __global__ void __launch_bounds__(1024)
 k_find_valid(int n, const double2* __restrict__ world, int ring_start, int cap, double vx, double vy,
              uint8_t* __restrict__ valid, int use_lds, int* __restrict__ scratch, Geom g, uint8_t* __restrict__ grid,
@@ -3280,11 +3291,8 @@ k_find_valid(int n, const double2* __restrict__ world, int ring_start, int cap, 
       const int i = i0 + tid;
       uint32_t idx = 0xFFFFFFFFu;
       if (i < n && v[i]) {
-        const double2 q = p[i];
-        const int gx = world_to_grid(q.x, g.off_x, g.scale);
-        const int gy = world_to_grid(q.y, g.off_y, g.scale);
-        if (gx >= 0 && gx < g.roi_w && gy >= 0 && gy < g.roi_h)  // IsUpTo on the ROI (Mapper.cpp:724-729)
-          idx = (uint32_t)((gx + g.border) + (gy + g.border) * g.stride);
+        int gx, gy;
+        if (base_point_cell(p[i], g, gx, gy)) idx = (uint32_t)((gx + g.border) + (gy + g.border) * g.stride);
       }
       const uint32_t left = (uint32_t)__shfl_up((int)idx, 1);  // neighbouring beams mostly hit the same cell
       if (idx != 0xFFFFFFFFu && ((tid & 63) == 0 || left != idx)) grid[idx] = (uint8_t)mark_value;
@@ -3629,10 +3637,8 @@ k_mark_centres(int B, int n, const double2* __restrict__ world, int ring_start, 
   const int b = blockIdx.y;
   uint32_t idx = 0xFFFFFFFFu;  // no cell
   if (i < n && valid[(size_t)b * n + i]) {
-    const double2 p = world[(size_t)((ring_start + b) % cap) * n + i];
-    const int gx = world_to_grid(p.x, g.off_x, g.scale);
-    const int gy = world_to_grid(p.y, g.off_y, g.scale);
-    if (gx >= 0 && gx < g.roi_w && gy >= 0 && gy < g.roi_h)  // IsUpTo on the ROI (:724-729)
+    int gx, gy;
+    if (base_point_cell(world[(size_t)((ring_start + b) % cap) * n + i], g, gx, gy))
       idx = (uint32_t)((gx + g.border) + (gy + g.border) * g.stride);
   }
   // neighbouring beams mostly hit the same cell: only the first lane of such a run goes for the CAS
@@ -3704,9 +3710,8 @@ __global__ void k_add_scans_serial(int B, int n, const double2* __restrict__ wor
   for (int i = 0; i < B * n; i++) {
     if (!valid[i]) continue;
     const double2 wp = world[(size_t)((ring_start + i / n) % cap) * n + (i % n)];
-    int gx = world_to_grid(wp.x, g.off_x, g.scale);
-    int gy = world_to_grid(wp.y, g.off_y, g.scale);
-    if (gx < 0 || gx >= g.roi_w || gy < 0 || gy >= g.roi_h) continue;
+    int gx, gy;
+    if (!base_point_cell(wp, g, gx, gy)) continue;
     size_t idx = (size_t)(gx + g.border) + (size_t)(gy + g.border) * g.stride;
     if (grid[idx] == kOccupied) continue;
     grid[idx] = kOccupied;

@@ -133,10 +133,12 @@ def test_errors_and_forget(ctx):
 
 @pytest.mark.parametrize("kw", [dict(resolution=0.05, smear_deviation=0.45, search_size=1.0, range_threshold=20.0),   # 37x37 smear
                                 dict(resolution=0.025, smear_deviation=0.03, search_size=0.5, range_threshold=20.0),  # 5x5
-                                dict(search_size=8.0, resolution=0.05, range_threshold=20.0)])                        # loop-sized lattice
+                                dict(search_size=8.0, resolution=0.05, range_threshold=20.0),                         # loop-sized lattice
+                                dict(resolution=0.05, smear_deviation=0.5, search_size=1.0, range_threshold=8.0)])    # 41x41, serial
 def test_other_configurations(ctx, kw):
     """Wide smear kernels take the listed scatter path (the cache gathers the window into a contiguous workspace for it);
-    the loop matcher's lattice goes through the dense kernels."""
+    the loop matcher's lattice goes through the dense kernels; a smear deviation of 10 x resolution puts 100 off the kernel's
+    centre, and the order-dependent k_add_scans_serial builds the grid."""
     plain, cached, cache = _pair(ctx, **dict(kw))
     ranges, odo = _trajectory(10, 14)
     for i in range(8):
