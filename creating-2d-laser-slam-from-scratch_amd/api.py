@@ -301,6 +301,191 @@ class FeatureExtractor:
         return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
 
 
+PLICP_MAX_READINGS = 2048  # LSLAM_PLICP_MAX_READINGS
+PLICP_RECORD = np.dtype([("x", "f8", 3), ("error", "f8"), ("valid", "i4"), ("iterations", "i4"), ("nvalid", "i4"),
+                         ("reserved", "i4")])  # lslam_plicp_record
+PLICP_ODOM_RECORD = np.dtype([("x", "f8", 3), ("error", "f8"), ("valid", "i4"), ("iterations", "i4"), ("nvalid", "i4"),
+                              ("flags", "i4"), ("base_in_odom", "f8", 3), ("reserved", "f8")])  # lslam_plicp_odom_record
+PLICP_ODOM_TRACK = np.dtype([("base_in_odom", "f8", 3), ("keyframe", "f8", 3), ("velocity", "f8", 2), ("last_icp_time", "f8"),
+                             ("scan_count", "i4"), ("initialized", "i4")])  # lslam_plicp_odom_track
+assert (PLICP_RECORD.itemsize, PLICP_ODOM_RECORD.itemsize, PLICP_ODOM_TRACK.itemsize) == (48, 80, 80)
+
+
+class PlicpParams(C.Structure):
+    """lslam_plicp_params: the sm_params sm_icp reads (scan_match_plicp.cc:43-156)."""
+
+    _fields_ = [(k, C.c_double) for k in (
+        "max_angular_correction_deg", "max_linear_correction", "epsilon_xy", "epsilon_theta", "max_correspondence_dist",
+        "outliers_maxPerc", "outliers_adaptive_order", "outliers_adaptive_mult")] + [(k, C.c_int32) for k in (
+            "max_iterations", "use_point_to_line_distance", "outliers_remove_doubles", "reserved")]
+
+
+def plicp_params(**kw) -> PlicpParams:
+    """Library defaults (lslam_plicp_params_defaults) with keyword overrides."""
+    p = PlicpParams()
+    lib().lslam_plicp_params_defaults(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class PlicpMatcher:
+    """lslam_plicp: lesson3's ScanMatchWithPLICP for many scan pairs per launch.  Parity with the reference is unpinned (its
+    arithmetic is the un-vendored csm): the results are defined by tools/plicp_cpu.py's sm_icp.  Equal distances rank by sens
+    order."""
+
+    def __init__(self, ctx: "Context", params: PlicpParams | None = None, laser=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.params = params if params is not None else plicp_params()
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_plicp_create(ctx.h, C.byref(self.params), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        if laser is not None:
+            self.set_laser(laser.angle_min, laser.angle_increment, laser.range_min, laser.range_max)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_plicp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def set_laser(self, angle_min: float, angle_increment: float, range_min: float, range_max: float):
+        self.ctx.check(self.L.lslam_plicp_set_laser(self.h, float(angle_min), float(angle_increment), float(range_min),
+                                                    float(range_max)))
+
+    def match_batch(self, ranges, pair_ref, pair_sens, first_guess=None, n_readings=None, out=None):
+        """ranges: [n_scans, stride] float32; pair b matches scan pair_sens[b] against scan pair_ref[b]; first_guess:
+        [n_pairs, 3] float64 or None (zeros) -> PLICP_RECORD[n_pairs]."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        if r.ndim != 2:
+            raise ValueError("ranges must be [n_scans, stride]")
+        n, stride = r.shape
+        nr = stride if n_readings is None else int(n_readings)
+        pr = np.ascontiguousarray(pair_ref, dtype=np.int32)
+        ps = np.ascontiguousarray(pair_sens, dtype=np.int32)
+        if pr.shape != ps.shape or pr.ndim != 1:
+            raise ValueError("pair_ref and pair_sens must be two [n_pairs] arrays")
+        g = None if first_guess is None else _f64(first_guess).reshape(len(pr), 3)
+        rec = np.zeros(len(pr), PLICP_RECORD) if out is None else out
+        self.ctx.check(self.L.lslam_plicp_match_batch(self.h, n, nr, r.ctypes.data, stride, len(pr), pr.ctypes.data, ps.ctypes.data,
+                                                      None if g is None else g.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def match_consecutive(self, ranges, n_readings=None):
+        """Every scan against the one before it: PLICP_RECORD[n_scans - 1], record k = scan k + 1 in scan k's frame."""
+        n = len(ranges)
+        idx = np.arange(max(n - 1, 0), dtype=np.int32)
+        return self.match_batch(ranges, idx, idx + 1, None, n_readings)
+
+    def match_batch_dev(self, n_scans: int, n_readings: int, ranges_ptr: int, ranges_stride: int, pair_ref, pair_sens,
+                        first_guess_ptr, records_ptr: int):
+        """The same with ranges, first guesses (may be None) and records in HBM: asynchronous on the context's stream, no host
+        wait.  The pair indices are host arrays."""
+        pr = np.ascontiguousarray(pair_ref, dtype=np.int32)
+        ps = np.ascontiguousarray(pair_sens, dtype=np.int32)
+        self.ctx.check(self.L.lslam_plicp_match_batch_dev(self.h, n_scans, n_readings, ranges_ptr, ranges_stride, len(pr),
+                                                          pr.ctypes.data, ps.ctypes.data, first_guess_ptr, records_ptr))
+
+    def debug_iteration(self, ranges_ref, ranges_sens, x_in=(0.0, 0.0, 0.0)):
+        """One iteration from x_in -> (j1, j2 int32 [n] reading indices or -1, flags uint8 [n], x_out [3], NaN at an early
+        exit).  Flags: 1 valid reading, 2 accepted before outlier rejection, 4 kept after it."""
+        a = np.ascontiguousarray(ranges_ref, dtype=np.float32)
+        b = np.ascontiguousarray(ranges_sens, dtype=np.float32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("two scans of one length")
+        n = len(a)
+        j1, j2 = np.full(n, -2, np.int32), np.full(n, -2, np.int32)
+        flags = np.zeros(n, np.uint8)
+        x = _f64(x_in)
+        x_out = np.zeros(3)
+        self.ctx.check(self.L.lslam_plicp_debug_iteration(self.h, a.ctypes.data, b.ctypes.data, n, x.ctypes.data, j1.ctypes.data,
+                                                          j2.ctypes.data, flags.ctypes.data, x_out.ctypes.data))
+        return j1, j2, flags, x_out
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_plicp_stats(self.h, out))
+        return dict(zip(("pairs", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
+class PlicpOdometry:
+    """lslam_plicp_odom: plicp_odometry.cc's node (keyframe scan matching, constant-velocity first guess) for n_tracks
+    independent tracks, one launch and one host wait per call.  An invalid match leaves the pose untouched (corr_ch = identity);
+    the prediction is the reference's, literally: linear.x only, nothing for a negative speed."""
+
+    def __init__(self, ctx: "Context", n_tracks: int = 1, params: PlicpParams | None = None, kf_dist_linear: float = 0.1,
+                 kf_dist_angular: float = 5.0 * (math.pi / 180.0), kf_scan_count: int = 10, base_to_laser=(0.0, 0.0, 0.0),
+                 laser=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.params = params if params is not None else plicp_params()
+        self.n_tracks = int(n_tracks)
+        b2l = _f64(base_to_laser)
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_plicp_odom_create(ctx.h, C.byref(self.params), self.n_tracks, float(kf_dist_linear),
+                                                 float(kf_dist_angular), int(kf_scan_count), b2l.ctypes.data, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        if laser is not None:
+            self.set_laser(laser.angle_min, laser.angle_increment, laser.range_min, laser.range_max)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_plicp_odom_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def set_laser(self, angle_min: float, angle_increment: float, range_min: float, range_max: float):
+        self.ctx.check(self.L.lslam_plicp_odom_set_laser(self.h, float(angle_min), float(angle_increment), float(range_min),
+                                                         float(range_max)))
+
+    def reset(self):
+        self.ctx.check(self.L.lslam_plicp_odom_reset(self.h))
+
+    def process_many(self, ranges, stamps, active=None, n_readings=None):
+        """ranges: [n_steps, n_tracks, stride] float32, stamps: [n_steps, n_tracks] seconds, active: [n_steps, n_tracks] or None
+        -> PLICP_ODOM_RECORD[n_steps, n_tracks]."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        if r.ndim == 2 and self.n_tracks == 1:
+            r = r[:, None, :]
+        if r.ndim != 3 or r.shape[1] != self.n_tracks:
+            raise ValueError("ranges must be [n_steps, n_tracks, stride]")
+        steps, _, stride = r.shape
+        nr = stride if n_readings is None else int(n_readings)
+        st = _f64(stamps).reshape(steps, self.n_tracks)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8).reshape(steps, self.n_tracks)
+        rec = np.zeros((steps, self.n_tracks), PLICP_ODOM_RECORD)
+        self.ctx.check(self.L.lslam_plicp_odom_process_many(self.h, steps, nr, r.ctypes.data, stride, st.ctypes.data,
+                                                            None if act is None else act.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def state(self) -> np.ndarray:
+        out = np.zeros(self.n_tracks, PLICP_ODOM_TRACK)
+        self.ctx.check(self.L.lslam_plicp_odom_state(self.h, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_plicp_odom_stats(self.h, out))
+        return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
 class GMapGeometry(C.Structure):
     _fields_ = [("map_size_x", C.c_int32), ("map_size_y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("size_x2", C.c_int32), ("size_y2", C.c_int32), ("patches_x", C.c_int32), ("patches_y", C.c_int32),
@@ -517,6 +702,24 @@ def lib() -> C.CDLL:
     L.lslam_features_stats.argtypes = [vp, vp]
     L.lslam_features_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.lslam_features_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.lslam_plicp_params_defaults.argtypes = [C.POINTER(PlicpParams)]
+    L.lslam_plicp_params_defaults.restype = None
+    L.lslam_plicp_create.argtypes = [vp, C.POINTER(PlicpParams), C.POINTER(vp)]
+    L.lslam_plicp_destroy.argtypes = [vp]
+    L.lslam_plicp_destroy.restype = None
+    L.lslam_plicp_set_laser.argtypes = [vp, dbl, dbl, dbl, dbl]
+    L.lslam_plicp_match_batch.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.lslam_plicp_match_batch_dev.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.lslam_plicp_debug_iteration.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.lslam_plicp_stats.argtypes = [vp, vp]
+    L.lslam_plicp_odom_create.argtypes = [vp, C.POINTER(PlicpParams), i32, dbl, dbl, i32, vp, C.POINTER(vp)]
+    L.lslam_plicp_odom_destroy.argtypes = [vp]
+    L.lslam_plicp_odom_destroy.restype = None
+    L.lslam_plicp_odom_set_laser.argtypes = [vp, dbl, dbl, dbl, dbl]
+    L.lslam_plicp_odom_reset.argtypes = [vp]
+    L.lslam_plicp_odom_state.argtypes = [vp, vp]
+    L.lslam_plicp_odom_process_many.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
+    L.lslam_plicp_odom_stats.argtypes = [vp, vp]
     L.lslam_map_set_cloud.argtypes = [vp, vp, vp, i32, C.POINTER(HectorScan), C.POINTER(i32)]
     L.lslam_hector_process_many_deskewed.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp]

@@ -719,6 +719,124 @@ class LaserScanFeaturesGpu {
   std::vector<lslam_feature_record> records_;
 };
 
+// lesson3's ScanMatchPLICP (lesson3/src/scan_match_plicp.cc) on the GPU: ScanCallback matches every scan against the one
+// before it (ScanMatchWithPLICP :266-300, zero first guess); MatchPairs is the batch form.  Parity with the reference is
+// unpinned (its arithmetic is the un-vendored csm); the results are defined by tools/plicp_cpu.py (see lslam_gpu.h).
+class ScanMatchPLICPGpu {
+ public:
+  // the LaserScan header fields LaserScanToLDP reads; params NULL = the node's InitParams
+  ScanMatchPLICPGpu(lslam_context* ctx, double angleMin, double angleIncrement, double rangeMin, double rangeMax,
+                    const lslam_plicp_params* params = nullptr)
+      : ctx_(ctx) {
+    lslam_plicp_params p;
+    if (params) p = *params; else lslam_plicp_params_defaults(&p);
+    check(lslam_plicp_create(ctx, &p, &h_));
+    const int rc = lslam_plicp_set_laser(h_, angleMin, angleIncrement, rangeMin, rangeMax);
+    if (rc != LSLAM_OK) {
+      lslam_plicp_destroy(h_);
+      check(rc);
+    }
+  }
+  ~ScanMatchPLICPGpu() { lslam_plicp_destroy(h_); }
+  ScanMatchPLICPGpu(const ScanMatchPLICPGpu&) = delete;
+  ScanMatchPLICPGpu& operator=(const ScanMatchPLICPGpu&) = delete;
+
+  // One scan of n beams.  The first scan only becomes the previous one (false, *out zeroed: initialized_, :205-214);
+  // afterwards *out is the pose of this scan in the previous scan's frame, and this scan becomes the previous one.  Every
+  // scan must have the first one's beam count (std::invalid_argument otherwise).  Both scans of the pair go up with each call;
+  // a log that is there as a whole is cheaper through MatchConsecutive.
+  bool ScanCallback(const float* ranges, int n, lslam_plicp_record* out) {
+    std::memset(out, 0, sizeof *out);
+    if (n < 0 || !ranges) throw std::invalid_argument("ScanMatchPLICPGpu::ScanCallback: a scan is required");
+    if (!initialized_) {
+      prev_.assign(ranges, ranges + n);
+      initialized_ = true;
+      return false;
+    }
+    if ((int)prev_.size() != n) throw std::invalid_argument("ScanMatchPLICPGpu::ScanCallback: the beam count changed");
+    two_.resize(2 * (size_t)n);
+    std::memcpy(two_.data(), prev_.data(), (size_t)n * sizeof(float));
+    std::memcpy(two_.data() + n, ranges, (size_t)n * sizeof(float));
+    const int32_t ref = 0, sens = 1;
+    check(lslam_plicp_match_batch(h_, 2, n, two_.data(), n, 1, &ref, &sens, nullptr, out));
+    prev_.assign(ranges, ranges + n);
+    return true;
+  }
+  // nPairs pairs over nScans scans (row k at ranges + k * rangesStride): pair b = scan pairSens[b] against scan pairRef[b];
+  // firstGuess (nPairs x 3) may be NULL
+  void MatchPairs(int nScans, int nReadings, const float* ranges, int rangesStride, int nPairs, const int32_t* pairRef,
+                  const int32_t* pairSens, const double* firstGuess, lslam_plicp_record* out) {
+    check(lslam_plicp_match_batch(h_, nScans, nReadings, ranges, rangesStride, nPairs, pairRef, pairSens, firstGuess, out));
+  }
+  // every scan against the one before it: out has nScans - 1 records
+  void MatchConsecutive(int nScans, int nReadings, const float* ranges, int rangesStride, lslam_plicp_record* out) {
+    if (nScans < 2) return;
+    idx_.resize((size_t)nScans);
+    for (int k = 0; k < nScans; k++) idx_[k] = k;
+    MatchPairs(nScans, nReadings, ranges, rangesStride, nScans - 1, idx_.data(), idx_.data() + 1, nullptr, out);
+  }
+  // {pairs matched, kernel launches, buffer growths, host waits}
+  void stats(int64_t out[4]) const { lslam_plicp_stats(h_, out); }
+  lslam_plicp* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_plicp* h_ = nullptr;
+  bool initialized_ = false;
+  std::vector<float> prev_, two_;
+  std::vector<int32_t> idx_;
+};
+
+// lesson3's keyframe odometry node (lesson3/src/plicp_odometry.cc) on the GPU for nTracks independent tracks.
+class PlicpOdometryGpu {
+ public:
+  PlicpOdometryGpu(lslam_context* ctx, int nTracks, double angleMin, double angleIncrement, double rangeMin, double rangeMax,
+                   const double baseToLaser[3] = nullptr, double kfDistLinear = 0.1,
+                   double kfDistAngular = 5.0 * (3.14159265358979323846 / 180.0), int kfScanCount = 10,
+                   const lslam_plicp_params* params = nullptr)
+      : ctx_(ctx), tracks_(nTracks) {
+    lslam_plicp_params p;
+    if (params) p = *params; else lslam_plicp_params_defaults(&p);
+    check(lslam_plicp_odom_create(ctx, &p, nTracks, kfDistLinear, kfDistAngular, kfScanCount, baseToLaser, &h_));
+    const int rc = lslam_plicp_odom_set_laser(h_, angleMin, angleIncrement, rangeMin, rangeMax);
+    if (rc != LSLAM_OK) {
+      lslam_plicp_odom_destroy(h_);
+      check(rc);
+    }
+  }
+  ~PlicpOdometryGpu() { lslam_plicp_odom_destroy(h_); }
+  PlicpOdometryGpu(const PlicpOdometryGpu&) = delete;
+  PlicpOdometryGpu& operator=(const PlicpOdometryGpu&) = delete;
+
+  // one scan of a one-track odometry (ScanCallback, :191-232)
+  void ScanCallback(const float* ranges, int n, double stamp, lslam_plicp_odom_record* out) {
+    ProcessMany(1, n, ranges, n, &stamp, nullptr, out);
+  }
+  // nSteps scans per track, every per-scan array indexed step * nTracks + track; active may be NULL (all 1)
+  void ProcessMany(int nSteps, int nReadings, const float* ranges, int rangesStride, const double* stamps,
+                   const uint8_t* active, lslam_plicp_odom_record* out) {
+    check(lslam_plicp_odom_process_many(h_, nSteps, nReadings, ranges, rangesStride, stamps, active, out));
+  }
+  void Reset() { check(lslam_plicp_odom_reset(h_)); }
+  // out: nTracks states
+  void State(lslam_plicp_odom_track* out) { check(lslam_plicp_odom_state(h_, out)); }
+  int tracks() const { return tracks_; }
+  // {scans processed, kernel launches, buffer growths, host waits}
+  void stats(int64_t out[4]) const { lslam_plicp_odom_stats(h_, out); }
+  lslam_plicp_odom* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  int tracks_;
+  lslam_plicp_odom* h_ = nullptr;
+};
+
 // gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's
 // ComputeMap (gmapping.cc:171-242).  cell() reads from a host copy of the counters, refreshed after every change.
 struct IntPoint2 {  // gmapping::IntPoint

@@ -1107,6 +1107,133 @@ int lslam_features_batch_dev(lslam_features* f, int n_scans, int n_readings, con
 /* out = {scans extracted, kernel launches, buffer growths (device or pinned), host waits} */
 int lslam_features_stats(const lslam_features* f, int64_t out[4]);
 
+/* ---------------------------------------------------------------------------------------- */
+/* lesson3 PL-ICP scan-to-scan matching (ScanMatchPLICP: lesson3/src/scan_match_plicp.cc and  */
+/* lesson3/src/plicp_odometry.cc, "O/" below), many pairs per launch, and the node's keyframe */
+/* odometry for many tracks per launch.                                                       */
+/* STANDING: PARITY WITH THE REFERENCE IS UNPINNED.  Its arithmetic lives in the un-vendored   */
+/* third-party library csm (sm_icp).  The results are DEFINED by this          */
+/* project's own fp64 restatement of the published algorithm (A. Censi, ICRA 2008): `sm_icp`   */
+/* in tools/plicp_cpu.py -- exhaustive nearest-neighbour search, duplicate / trimmed /         */
+/* adaptive outlier rejection, closed-form point-to-line minimiser.  The wrapper logic of the  */
+/* two reference files is followed literally.  All device arithmetic is fp64.                  */
+/* Three deliberate rules, and a fourth fact about the definition:                            */
+/*  1. RANK TIES: the trimmed cut and the adaptive percentile go by rank; among EQUAL          */
+/*     distances the LOWER sens order ranks first (sens order = the reading's position among   */
+/*     the valid readings of the sens scan).  The same (distance, sens order) order decides    */
+/*     which of two sens points on one ref point survives "remove doubles".                    */
+/*  2. INVALID MATCH: where sm_icp reports valid = 0 the reference reads an uninitialised      */
+/*     corr_ch (O/:397-423).  Here corr_ch is the IDENTITY and the pose and velocity are left   */
+/*     untouched; NewKeyframeNeeded still counts the scan.                                     */
+/*  3. LITERAL PREDICTION: GetPrediction (O/:442-456) reads linear.y and linear.z, which        */
+/*     nothing ever sets, so the prediction is (v.linear.x < 1e-6 ? 0 : dt * v.linear.x, 0, 0): */
+/*     no angular prediction, and a negative speed predicts nothing.                           */
+/*  4. THE HELPER'S QUARTIC: the polynomial in lambda that sm_icp's solve hands to np.roots is   */
+/*     (2L+2e0)^2 (2L+2e1)^2 - 4 (hp0^2+hp1^2) L - 4 (hp0^2 e1^2 + hp1^2 e0^2) -- numpy multiplies */
+/*     a float64 scalar into a poly1d element by element -- and not the Lagrange condition of    */
+/*     the paper.  The helper defines the results, so this is the polynomial solved here: all    */
+/*     its real roots, the lowest-cost one.                                     */
+/* ---------------------------------------------------------------------------------------- */
+#define LSLAM_PLICP_MAX_READINGS 2048
+/* the sm_params sm_icp reads; defaults = ScanMatchPLICP::InitParams (scan_match_plicp.cc:43-156) */
+typedef struct lslam_plicp_params {
+  double max_angular_correction_deg; /* 45.0 */
+  double max_linear_correction;      /* 1.0 */
+  double epsilon_xy;                 /* 0.000001 */
+  double epsilon_theta;              /* 0.000001 */
+  double max_correspondence_dist;    /* 1.0 */
+  double outliers_maxPerc;           /* 0.90 */
+  double outliers_adaptive_order;    /* 0.7 */
+  double outliers_adaptive_mult;     /* 2.0 */
+  int32_t max_iterations;            /* 10 */
+  int32_t use_point_to_line_distance; /* 1 */
+  int32_t outliers_remove_doubles;   /* 1 */
+  int32_t reserved;
+} lslam_plicp_params;
+void lslam_plicp_params_defaults(lslam_plicp_params* p);
+/* sm_result's fields the node reads (scan_match_plicp.cc:285-300).  sm_icp's early exits (fewer than 3 valid readings on a
+ * side, fewer than 3 correspondences after either rejection step, a singular solve) give the zero record with error = +inf;
+ * a result beyond max_linear_correction / max_angular_correction_deg of the first guess has valid = 0 with x still reported. */
+typedef struct lslam_plicp_record {
+  double x[3];        /* the pose of the sens scan in the ref scan's frame */
+  double error;       /* the sum of squared point-to-line residuals of the last iteration */
+  int32_t valid;
+  int32_t iterations;
+  int32_t nvalid;     /* correspondences of the last iteration */
+  int32_t reserved;
+} lslam_plicp_record; /* 48 bytes */
+typedef struct lslam_plicp lslam_plicp;
+int lslam_plicp_create(lslam_context* ctx, const lslam_plicp_params* params, lslam_plicp** out);
+void lslam_plicp_destroy(lslam_plicp* h);
+/* LaserScanToLDP's header fields (scan_match_plicp.cc:220-261): a reading is valid iff range_min < r < range_max (NaN is
+ * invalid), theta_i = angle_min + i * angle_increment in double.  The cos / sin table is built once per geometry, as
+ * CreateCache (O/:237-252) does, and kept by the handle. */
+int lslam_plicp_set_laser(lslam_plicp* h, double angle_min, double angle_increment, double range_min, double range_max);
+/* ScanMatchWithPLICP (scan_match_plicp.cc:266-300) for n_pairs pairs in ONE launch (a workgroup per pair, the iterations loop
+ * on the device).  ranges: n_scans rows of n_readings float32, row k at ranges + k * ranges_stride (the matcher's and the
+ * de-skew's block layout); pair b matches scan pair_sens[b] against scan pair_ref[b], so a log uploads each scan once.
+ * first_guess: n_pairs x 3 doubles, NULL = zeros (as :266-300).  out: n_pairs records.  pair_ref / pair_sens are HOST arrays
+ * in both forms.  The host form owns its buffers (a repeated shape allocates nothing) and waits once, at its end.  The _dev
+ * form takes ranges, first_guess and out in HBM, is ASYNCHRONOUS on lslam_stream() and makes no host wait -- with one
+ * back-pressure: the pair indices go up through a ring of 4 pinned slots, so a call that would reuse a slot whose launch has
+ * not finished (the fifth of five queued calls), or that brings more pairs than any call before it (every slot grows), waits
+ * for that launch first; such waits are counted in the stats.  A pair's record is
+ * byte for byte the same alone and in any batch.  n_pairs == 0 is LSLAM_OK and launches nothing.
+ * LSLAM_ERR_INVALID_ARGUMENT, outputs untouched: NULL pointers, a pair index outside [0, n_scans), no laser set.
+ * LSLAM_ERR_UNSUPPORTED: more than LSLAM_PLICP_MAX_READINGS readings. */
+int lslam_plicp_match_batch(lslam_plicp* h, int n_scans, int n_readings, const float* ranges, int ranges_stride, int n_pairs,
+                            const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess, lslam_plicp_record* out);
+int lslam_plicp_match_batch_dev(lslam_plicp* h, int n_scans, int n_readings, const float* ranges_dev, int ranges_stride, int n_pairs,
+                                const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess_dev,
+                                lslam_plicp_record* out_dev);
+/* ONE iteration of sm_icp from x_in, by the same device code as the batch kernel (host pointers; one launch, one wait).
+ * Per reading of the sens scan: j1, j2 = the ref READING indices of the segment (-1 where none), flags bit 0 = valid reading,
+ * bit 1 = correspondence accepted before outlier rejection, bit 2 = kept after doubles / trimmed / adaptive rejection.
+ * x_out = the solved pose, NaN where the iteration took one of sm_icp's early exits. */
+int lslam_plicp_debug_iteration(lslam_plicp* h, const float* ranges_ref, const float* ranges_sens, int n, const double x_in[3],
+                                int32_t* j1, int32_t* j2, uint8_t* flags, double x_out[3]);
+/* out = {pairs matched, kernel launches, buffer growths (device or pinned), host waits} */
+int lslam_plicp_stats(const lslam_plicp* h, int64_t out[4]);
+
+/* The node of O/ (ScanCallback :191-232, ScanMatchWithPLICP :327-436, NewKeyframeNeeded :498-517) for n_tracks independent
+ * tracks (robots or logs): ONE launch per call, a workgroup per track walking its scans in order; the state stays on the
+ * device, the keyframe scan in HBM; one host wait per call.  kf_dist_linear 0.1, kf_dist_angular 5 deg * pi / 180,
+ * kf_scan_count 10 (O/:64-67); base_to_laser: the planar base <- laser transform (x, y, yaw), NULL = identity. */
+typedef struct lslam_plicp_odom_record {
+  double x[3];        /* sm_icp's result against the keyframe scan, as lslam_plicp_record */
+  double error;
+  int32_t valid;
+  int32_t iterations; /* -1: an inactive scan (every other field zero) */
+  int32_t nvalid;
+  int32_t flags;      /* bit 0: the first scan of the track, no match made; bit 1: this scan became the keyframe */
+  double base_in_odom[3];
+  double reserved;
+} lslam_plicp_odom_record; /* 80 bytes */
+typedef struct lslam_plicp_odom_track {
+  double base_in_odom[3];
+  double keyframe[3];  /* base_in_odom_keyframe_ */
+  double velocity[2];  /* latest_velocity_.linear.x, .angular.z */
+  double last_icp_time;
+  int32_t scan_count;
+  int32_t initialized;
+} lslam_plicp_odom_track; /* 80 bytes */
+typedef struct lslam_plicp_odom lslam_plicp_odom;
+int lslam_plicp_odom_create(lslam_context* ctx, const lslam_plicp_params* params, int n_tracks, double kf_dist_linear,
+                            double kf_dist_angular, int kf_scan_count, const double base_to_laser[3], lslam_plicp_odom** out);
+void lslam_plicp_odom_destroy(lslam_plicp_odom* h);
+int lslam_plicp_odom_set_laser(lslam_plicp_odom* h, double angle_min, double angle_increment, double range_min, double range_max);
+/* every track back to its state after create (asynchronous) */
+int lslam_plicp_odom_reset(lslam_plicp_odom* h);
+/* out: n_tracks states (one host wait) */
+int lslam_plicp_odom_state(lslam_plicp_odom* h, lslam_plicp_odom_track* out);
+/* n_steps scans per track; every per-scan array is indexed step * n_tracks + track: ranges rows (float32, ranges_stride
+ * apart), stamps (seconds), active (NULL = all 1; an inactive scan changes nothing of its track), out.  Host pointers.  Every
+ * call of one handle between resets takes the same n_readings. */
+int lslam_plicp_odom_process_many(lslam_plicp_odom* h, int n_steps, int n_readings, const float* ranges, int ranges_stride,
+                                  const double* stamps, const uint8_t* active, lslam_plicp_odom_record* out);
+/* out = {scans processed, kernel launches, buffer growths, host waits} */
+int lslam_plicp_odom_stats(const lslam_plicp_odom* h, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
