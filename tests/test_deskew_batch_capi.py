@@ -4,11 +4,11 @@ LidarUndistortionGpu, HectorSlamProcessorGpu::updateManyDeskewed, include/lslam_
 and link against liblslam_gpu.so.  No device needed; on a GPU box the little program also runs a batch."""
 import pathlib
 import re
-import subprocess
 
 import pytest
 
-from lslam_amd import api, build
+import adapter_demo
+from lslam_amd import api
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 SYMBOLS = {
@@ -126,25 +126,15 @@ int main(int argc, char**) {
 '''
 
 
-def _build(tmp_path):
-    lib = build.build_library()
-    src = tmp_path / "deskew_demo.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "deskew_demo"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_deskew_adapters_compile_and_link(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "deskew_demo", SRC)
+    r = adapter_demo.run(exe)
     assert r.returncode == 0, r.stdout + r.stderr  # without a GPU it reports "no device" and exits 0
 
 
 @pytest.mark.gpu
 def test_deskew_adapters_run_on_gpu(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe), "need-gpu"], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "deskew_demo", SRC)
+    r = adapter_demo.run(exe, "need-gpu")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "deskew adapters ok" in r.stdout

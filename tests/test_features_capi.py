@@ -7,7 +7,8 @@ import subprocess
 
 import pytest
 
-from lslam_amd import api, build
+import adapter_demo
+from lslam_amd import api
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 SYMBOLS = {
@@ -120,25 +121,15 @@ int main(int argc, char**) {
 '''
 
 
-def _build(tmp_path):
-    lib = build.build_library()
-    src = tmp_path / "features_demo.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "features_demo"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_features_adapter_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "features_demo", SRC)
+    r = adapter_demo.run(exe)
     assert r.returncode == 0, r.stdout + r.stderr  # without a GPU it reports "no device" and exits 0
 
 
 @pytest.mark.gpu
 def test_features_adapter_runs_on_gpu(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe), "need-gpu"], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "features_demo", SRC)
+    r = adapter_demo.run(exe, "need-gpu")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "features adapter ok" in r.stdout

@@ -1,36 +1,15 @@
 """Every kernel of the GMapping count map (csrc/gmapping_map.hip) stays out of scratch memory, read from the compiler's own
 report in the device assembly (no GPU needed: hipcc cross-compiles)."""
-import pathlib
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-SRC = ROOT / "creating-2d-laser-slam-from-scratch_amd" / "csrc" / "gmapping_map.hip"
+import kernel_report
+
 KERNELS = {"k_gm_endpoint", "k_gm_trace", "k_gm_hist", "k_gm_scan", "k_gm_scatter", "k_gm_fold", "k_gm_reset", "k_gm_classify"}
 
 
 @pytest.mark.timeout(600)
-def test_gmapping_kernels_use_no_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not pathlib.Path(hipcc).exists():
-        pytest.skip("hipcc not available")
-    out = tmp_path / "gmapping_map.s"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-           "-o", str(out), str(SRC)]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    name, seen = None, {}
-    for line in out.read_text().splitlines():
-        m = re.match(r"^(_Z\S+):", line)
-        if m:
-            k = re.search(r"(k_gm_[a-z]+)", m.group(1))
-            name = k.group(1) if k else None
-            continue
-        m = re.search(r"; (ScratchSize|NumVgprs): (\d+)", line)
-        if name and m:
-            seen.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    assert set(seen) == KERNELS, seen
+def test_gmapping_kernels_use_no_scratch():
+    seen = {k: v.resources for k, v in kernel_report.report("gmapping_map.hip").items() if k[0].startswith("k_gm_")}
+    assert set(seen) == {(name, ()) for name in KERNELS}, seen
     for k, v in seen.items():
         assert v["ScratchSize"] == 0, (k, v)

@@ -1,13 +1,9 @@
 """MapRepGpu::matchDataBatch (include/lslam_adapters.hpp) compiles stand-alone with g++ and links against
 liblslam_gpu.so; on a GPU box the little program also runs a batch through it and compares with matchData."""
-import pathlib
-import subprocess
-
 import pytest
 
-from lslam_amd import build
+import adapter_demo
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
 SRC = r'''
 #include <cstdio>
 #include <cmath>
@@ -53,25 +49,15 @@ int main(int argc, char**) {
 '''
 
 
-def _build(tmp_path):
-    lib = build.build_library()
-    src = tmp_path / "gn_batch_demo.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "gn_batch_demo"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_match_data_batch_adapter_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "gn_batch_demo", SRC)
+    r = adapter_demo.run(exe)
     assert r.returncode == 0, r.stdout + r.stderr  # without a GPU it reports "no device" and exits 0
 
 
 @pytest.mark.gpu
 def test_match_data_batch_adapter_runs_on_gpu(tmp_path):
-    exe = _build(tmp_path)
-    r = subprocess.run([str(exe), "need-gpu"], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "gn_batch_demo", SRC)
+    r = adapter_demo.run(exe, "need-gpu")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "batch ok" in r.stdout

@@ -1,12 +1,8 @@
 """lslam::HectorSlamFleetGpu (include/lslam_adapters.hpp) compiles stand-alone with g++ and links against liblslam_gpu.so: a
 fleet that owns its processors, a fleet that borrows the caller's, update() for one step in the reference's container and
 pose shapes.  Compile-only: without a GPU the little program reports "no device" and exits 0."""
-import pathlib
-import subprocess
+import adapter_demo
 
-from lslam_amd import build
-
-ROOT = pathlib.Path(__file__).resolve().parent.parent
 SRC = r'''
 #include <cstdio>
 #include <cmath>
@@ -70,12 +66,7 @@ int main(int argc, char**) {
 
 
 def test_fleet_adapter_compiles_and_links(tmp_path):
-    lib = build.build_library()
-    src = tmp_path / "hector_fleet_demo.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "hector_fleet_demo"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "hector_fleet_demo", SRC)
+    r = adapter_demo.run(exe)
     assert r.returncode == 0, r.stdout + r.stderr  # without a GPU it reports "no device" and exits 0; with one it runs
     assert "no device" in r.stdout or "fleet ok" in r.stdout, r.stdout

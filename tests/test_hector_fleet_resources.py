@@ -2,47 +2,19 @@
 arguments from the fleet's tables costs the matcher no occupancy: every k_hf_match_* instantiation keeps at least the waves per
 SIMD of its k_hs_match_* counterpart in the same compile.  Read from the compiler's own report in the device assembly (no GPU
 needed: hipcc cross-compiles).  Resource metadata only."""
-import pathlib
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-CSRC = ROOT / "creating-2d-laser-slam-from-scratch_amd" / "csrc"
+import kernel_report
+
 PLAIN = {"k_hf_project", "k_hf_mark", "k_hf_apply"}
 MATCH = {"k_hf_match_reg": "k_hs_match_reg", "k_hf_match_fast": "k_hs_match_fast"}
-INSTANCES = {"k_hf_match_reg": {"ILi256ELi5EE", "ILi512ELi3EE", "ILi1024ELi2EE"}, "k_hf_match_fast": {"ILi256EE", "ILi512EE", "ILi1024EE"}}
+INSTANCES = {"k_hf_match_reg": {(256, 5), (512, 3), (1024, 2)}, "k_hf_match_fast": {(256,), (512,), (1024,)}}
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not pathlib.Path(hipcc).exists():
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("hf") / "logodds_map.s"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-           "-o", str(out), str(CSRC / "logodds_map.hip")]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+def report():
     want = PLAIN | set(MATCH) | set(MATCH.values())
-    key, seen = None, {}
-    for line in out.read_text().splitlines():
-        m = re.match(r"^(_Z\S+):", line)
-        if m:
-            # Itanium mangling: <length><identifier>, behind the anonymous namespace's "_GLOBAL__N_1"; a template's arguments
-            # follow the identifier (I ... E)
-            k = re.search(r"_GLOBAL__N_1(\d+)(k_\w+)", m.group(1))
-            key = None
-            if k:
-                name, rest = k.group(2)[:int(k.group(1))], k.group(2)[int(k.group(1)):]
-                if name in want:
-                    t = re.match(r"(I(?:Li\d+E)+E)", rest)
-                    key = (name, t.group(1) if t else "")
-            continue
-        m = re.search(r"; (ScratchSize|NumVgprs|NumSgprs|LDSByteSize|Occupancy): (\d+)", line)
-        if key and m:
-            seen.setdefault(key, {})[m.group(1)] = int(m.group(2))
+    seen = {k: v.resources for k, v in kernel_report.report("logodds_map.hip").items() if k[0] in want}
     for k in sorted(seen):
         print(k, seen[k])
     return seen

@@ -8,39 +8,18 @@ Bounds, from the launch shape and not from what the compiler happened to produce
   LDS      k_live_box: one record per wave of the block (the scan's box, 4 doubles, and the largest x and y its rays
            reach, 2 doubles) = 4 waves x 6 doubles = 192 bytes; the trace and regrid kernels use none (the beams of a wave
            travel by lane shuffles)"""
-import pathlib
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-SRC = ROOT / "creating-2d-laser-slam-from-scratch_amd" / "csrc" / "livemap.hip"
+import kernel_report
+
 LDS = {"k_live_box": 4 * 6 * 8, "k_live_trace": 0, "k_live_regrid": 0}
 
 
 @pytest.mark.timeout(600)
-def test_livemap_kernel_resources(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not pathlib.Path(hipcc).exists():
-        pytest.skip("hipcc not available")
-    out = tmp_path / "livemap.s"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-           "-o", str(out), str(SRC)]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    name, seen = None, {}
-    for line in out.read_text().splitlines():
-        m = re.match(r"^(_Z\S+):", line)
-        if m:
-            k = re.search(r"(k_live_[a-z]+)", m.group(1))
-            name = k.group(1) if k else None
-            continue
-        m = re.search(r"; (ScratchSize|NumVgprs|LDSByteSize): (\d+)", line)
-        if name and m:
-            seen.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    assert set(seen) == set(LDS), seen
+def test_livemap_kernel_resources():
+    seen = {k: v.resources for k, v in kernel_report.report("livemap.hip").items() if k[0].startswith("k_live_")}
+    assert set(seen) == {(name, ()) for name in LDS}, seen
     for k, v in seen.items():
         assert v["ScratchSize"] == 0, (k, v)
         assert v["NumVgprs"] <= 128, (k, v)
-        assert v["LDSByteSize"] == LDS[k], (k, v)
+        assert v["LDSByteSize"] == LDS[k[0]], (k, v)

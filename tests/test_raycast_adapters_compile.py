@@ -7,7 +7,7 @@ import subprocess
 
 import pytest
 
-from lslam_amd import build
+import adapter_demo
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 KARTO = pathlib.Path("/root/reference/lesson6/lib/open_karto")
@@ -78,13 +78,8 @@ double probe(lslam_context* ctx, const karto::LocalizedRangeScanVector& scans, c
 
 
 def test_raycaster_adapter_compiles_and_links(tmp_path):
-    lib = build.build_library()
-    src = tmp_path / "raycaster_demo.cpp"
-    src.write_text(SRC)
-    exe = tmp_path / "raycaster_demo"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = adapter_demo.build(tmp_path, "raycaster_demo", SRC)
+    r = adapter_demo.run(exe)
     assert r.returncode == 0, r.stdout + r.stderr  # without a GPU it reports "no device" and exits 0; with one it runs
     assert "no device" in r.stdout or "raycaster ok" in r.stdout, r.stdout
 

@@ -12,50 +12,29 @@ hipcc cross-compiles; the file is compiled ONCE for the module):
 The 256- and 1024-thread forms (small batches, the lone MatchScan) share the block function; they keep their own register
 regime and are held to no scratch."""
 import ctypes as C
-import pathlib
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-SRC = ROOT / "creating-2d-laser-slam-from-scratch_amd" / "csrc" / "scan_matcher.hip"
+import kernel_report
+
 LDS_PER_CU = 160 * 1024
 BLOCKS_PER_CU = 16  # 8 waves per SIMD x 4 SIMDs / 2 waves per block
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    """"k_reduce_coarse_lds<NT>" -> {ScratchSize, NumVgprs, TotalNumSgprs, LDSByteSize}"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not pathlib.Path(hipcc).exists():
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("resources") / "scan_matcher.s"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-           "-o", str(out), str(SRC)]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    name, seen = None, {}
-    for line in out.read_text().splitlines():
-        m = re.match(r"^(_Z\S+):", line)
-        if m:
-            k = re.search(r"\d+(k_reduce_coarse_lds)ILi(\d+)E", m.group(1))
-            name = "%s<%s>" % (k.group(1), k.group(2)) if k else None
-            continue
-        m = re.search(r"; (ScratchSize|NumVgprs|TotalNumSgprs|LDSByteSize): (\d+)", line)
-        if name and m:
-            seen.setdefault(name, {})[m.group(1)] = int(m.group(2))
-    return seen
+def report():
+    """(NT,) -> {ScratchSize, NumVgprs, TotalNumSgprs, LDSByteSize, ...} of k_reduce_coarse_lds<NT>"""
+    return {k[1]: v.resources for k, v in kernel_report.report("scan_matcher.hip").items() if k[0] == "k_reduce_coarse_lds"}
 
 
 @pytest.mark.timeout(600)
 def test_the_three_forms_are_built(report):
-    assert set(report) == {"k_reduce_coarse_lds<%d>" % nt for nt in (128, 256, 1024)}, report
+    assert set(report) == {(128,), (256,), (1024,)}, report
 
 
 @pytest.mark.timeout(600)
 def test_narrow_form_fits_eight_waves_per_simd(report):
-    r = report["k_reduce_coarse_lds<128>"]
+    r = report[(128,)]
     assert r["ScratchSize"] == 0, r
     assert r["NumVgprs"] <= 64, r
     assert r["TotalNumSgprs"] <= 80, r
@@ -71,11 +50,11 @@ def test_narrow_form_lds_admits_sixteen_blocks_per_cu(report):
     dyn = L.lslam_debug_reduce_lds_bytes(C.byref(cfg), 128, C.byref(dims))
     assert list(dims) == [11, 11, 21], list(dims)  # the headline geometry
     assert dyn > 0
-    static = report["k_reduce_coarse_lds<128>"]["LDSByteSize"]
+    static = report[(128,)]["LDSByteSize"]
     assert static + dyn <= LDS_PER_CU // BLOCKS_PER_CU, (static, dyn)
 
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("nt", [256, 1024])
 def test_wide_forms_stay_out_of_scratch(report, nt):
-    assert report["k_reduce_coarse_lds<%d>" % nt]["ScratchSize"] == 0, report
+    assert report[(nt,)]["ScratchSize"] == 0, report
