@@ -418,6 +418,149 @@ class PlicpMatcher:
         return dict(zip(("pairs", "launches", "growths", "host_waits"), (int(v) for v in out)))
 
 
+ICP_MAX_POINTS = 2048  # LSLAM_ICP_MAX_POINTS
+ICP_RECORD = np.dtype([("x", "f8", 3), ("fitness", "f8"), ("mse", "f8"), ("converged", "i4"), ("iterations", "i4"),
+                       ("ncorr", "i4"), ("state", "i4"), ("reserved", "f8")])  # lslam_icp_record
+assert ICP_RECORD.itemsize == 64
+
+
+class IcpParams(C.Structure):
+    """lslam_icp_params: what a default-configured pcl::IterativeClosestPoint reads (scan_match_icp.cc:135-164)."""
+
+    _fields_ = [(k, C.c_double) for k in (
+        "max_correspondence_distance", "transformation_epsilon", "euclidean_fitness_epsilon", "absolute_mse")] + [
+            (k, C.c_int32) for k in ("max_iterations", "skip_invalid", "invalid_as_nan", "reserved")]
+
+
+def icp_params(**kw) -> IcpParams:
+    """Library defaults (lslam_icp_params_defaults) with keyword overrides."""
+    p = IcpParams()
+    lib().lslam_icp_params_defaults(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class IcpMatcher:
+    """lslam_icp: lesson2's ConvertScan2PointCloud and ScanMatchWithICP for many scan pairs per launch.  Parity with the
+    reference is unpinned (its arithmetic is PCL's): the results are defined by tools/icp_cpu.py's icp.  Among equal distances
+    the lowest target index wins."""
+
+    def __init__(self, ctx: "Context", params: IcpParams | None = None, laser=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.params = params if params is not None else icp_params()
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_icp_create(ctx.h, C.byref(self.params), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+        if laser is not None:
+            self.set_laser(laser.angle_min, laser.angle_increment, laser.range_min, laser.range_max)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_icp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def set_laser(self, angle_min: float, angle_increment: float, range_min: float, range_max: float):
+        self.ctx.check(self.L.lslam_icp_set_laser(self.h, float(angle_min), float(angle_increment), float(range_min),
+                                                  float(range_max)))
+
+    @staticmethod
+    def _ranges(ranges, n_readings):
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        if r.ndim != 2:
+            raise ValueError("ranges must be [n_scans, stride]")
+        return r, r.shape[0], r.shape[1], (r.shape[1] if n_readings is None else int(n_readings))
+
+    @staticmethod
+    def _pairs(pair_source, pair_target, first_guess):
+        ps = np.ascontiguousarray(pair_source, dtype=np.int32)
+        pt = np.ascontiguousarray(pair_target, dtype=np.int32)
+        if ps.shape != pt.shape or ps.ndim != 1:
+            raise ValueError("pair_source and pair_target must be two [n_pairs] arrays")
+        g = None if first_guess is None else _f64(first_guess).reshape(len(ps), 3)
+        return ps, pt, g
+
+    def convert(self, ranges, n_readings=None):
+        """ranges: [n_scans, stride] float32 -> (xyz float32 [n_scans, n, 3], valid uint8 [n_scans, n])."""
+        r, n, stride, nr = self._ranges(ranges, n_readings)
+        xyz, valid = np.zeros((n, nr, 3), np.float32), np.zeros((n, nr), np.uint8)
+        self.ctx.check(self.L.lslam_icp_convert_batch(self.h, n, nr, r.ctypes.data, stride, xyz.ctypes.data, valid.ctypes.data))
+        return xyz, valid
+
+    def convert_dev(self, n_scans: int, n_readings: int, ranges_ptr: int, ranges_stride: int, xyz_ptr: int, valid_ptr: int):
+        self.ctx.check(self.L.lslam_icp_convert_batch_dev(self.h, n_scans, n_readings, ranges_ptr, ranges_stride, xyz_ptr, valid_ptr))
+
+    def match_batch(self, ranges, pair_source, pair_target, first_guess=None, n_readings=None, out=None):
+        """ranges: [n_scans, stride] float32; pair b aligns scan pair_source[b]'s cloud to scan pair_target[b]'s; first_guess:
+        [n_pairs, 3] float64 (x, y, yaw) or None (zeros) -> ICP_RECORD[n_pairs]."""
+        r, n, stride, nr = self._ranges(ranges, n_readings)
+        ps, pt, g = self._pairs(pair_source, pair_target, first_guess)
+        rec = np.zeros(len(ps), ICP_RECORD) if out is None else out
+        self.ctx.check(self.L.lslam_icp_match_batch(self.h, n, nr, r.ctypes.data, stride, len(ps), ps.ctypes.data, pt.ctypes.data,
+                                                    None if g is None else g.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def match_batch_dev(self, n_scans: int, n_readings: int, ranges_ptr: int, ranges_stride: int, pair_source, pair_target,
+                        first_guess_ptr, records_ptr: int):
+        """The same with ranges, first guesses (may be None) and records in HBM: asynchronous on the context's stream, no host
+        wait.  The pair indices are host arrays."""
+        ps, pt, _ = self._pairs(pair_source, pair_target, None)
+        self.ctx.check(self.L.lslam_icp_match_batch_dev(self.h, n_scans, n_readings, ranges_ptr, ranges_stride, len(ps),
+                                                        ps.ctypes.data, pt.ctypes.data, first_guess_ptr, records_ptr))
+
+    def match_clouds(self, xyz, pair_source, pair_target, valid=None, first_guess=None, out=None):
+        """xyz: [n_clouds, n, 3] float32, valid: [n_clouds, n] uint8 or None (read only with skip_invalid) -> ICP_RECORD[n_pairs]."""
+        c = np.ascontiguousarray(xyz, dtype=np.float32)
+        if c.ndim != 3 or c.shape[2] != 3:
+            raise ValueError("xyz must be [n_clouds, n, 3]")
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8).reshape(c.shape[0], c.shape[1])
+        ps, pt, g = self._pairs(pair_source, pair_target, first_guess)
+        rec = np.zeros(len(ps), ICP_RECORD) if out is None else out
+        self.ctx.check(self.L.lslam_icp_match_clouds(self.h, c.shape[0], c.shape[1], c.ctypes.data, None if v is None else v.ctypes.data,
+                                                     len(ps), ps.ctypes.data, pt.ctypes.data, None if g is None else g.ctypes.data,
+                                                     rec.ctypes.data))
+        return rec
+
+    def match_clouds_dev(self, n_clouds: int, n_points: int, xyz_ptr: int, valid_ptr, pair_source, pair_target, first_guess_ptr,
+                         records_ptr: int):
+        ps, pt, _ = self._pairs(pair_source, pair_target, None)
+        self.ctx.check(self.L.lslam_icp_match_clouds_dev(self.h, n_clouds, n_points, xyz_ptr, valid_ptr, len(ps), ps.ctypes.data,
+                                                         pt.ctypes.data, first_guess_ptr, records_ptr))
+
+    def debug_iteration(self, src_xyz, tgt_xyz, x_in=(0.0, 0.0, 0.0), src_valid=None, tgt_valid=None):
+        """One iteration from x_in -> (corr int32 [n] (-1: rejected or masked), d2 float64 [n], inc [3] = (tx, ty, theta), NaN
+        where fewer than 3 were accepted, mse, ncorr)."""
+        a = np.ascontiguousarray(src_xyz, dtype=np.float32)
+        b = np.ascontiguousarray(tgt_xyz, dtype=np.float32)
+        if a.shape != b.shape or a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("two [n, 3] clouds of one length")
+        n = len(a)
+        sv = None if src_valid is None else np.ascontiguousarray(src_valid, dtype=np.uint8).reshape(n)
+        tv = None if tgt_valid is None else np.ascontiguousarray(tgt_valid, dtype=np.uint8).reshape(n)
+        corr, d2, inc = np.full(n, -2, np.int32), np.zeros(n), np.zeros(3)
+        x, mse, ncorr = _f64(x_in), C.c_double(0.0), C.c_int32(0)
+        self.ctx.check(self.L.lslam_icp_debug_iteration(self.h, a.ctypes.data, b.ctypes.data, None if sv is None else sv.ctypes.data,
+                                                        None if tv is None else tv.ctypes.data, n, x.ctypes.data, corr.ctypes.data,
+                                                        d2.ctypes.data, inc.ctypes.data, C.byref(mse), C.byref(ncorr)))
+        return corr, d2, inc, mse.value, ncorr.value
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_icp_stats(self.h, out))
+        return dict(zip(("pairs", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
 class PlicpOdometry:
     """lslam_plicp_odom: plicp_odometry.cc's node (keyframe scan matching, constant-velocity first guess) for n_tracks
     independent tracks, one launch and one host wait per call.  An invalid match leaves the pose untouched (corr_ch = identity);
@@ -720,6 +863,20 @@ def lib() -> C.CDLL:
     L.lslam_plicp_odom_state.argtypes = [vp, vp]
     L.lslam_plicp_odom_process_many.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
     L.lslam_plicp_odom_stats.argtypes = [vp, vp]
+    L.lslam_icp_params_defaults.argtypes = [C.POINTER(IcpParams)]
+    L.lslam_icp_params_defaults.restype = None
+    L.lslam_icp_create.argtypes = [vp, C.POINTER(IcpParams), C.POINTER(vp)]
+    L.lslam_icp_destroy.argtypes = [vp]
+    L.lslam_icp_destroy.restype = None
+    L.lslam_icp_set_laser.argtypes = [vp, dbl, dbl, dbl, dbl]
+    L.lslam_icp_convert_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    L.lslam_icp_convert_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    L.lslam_icp_match_batch.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.lslam_icp_match_batch_dev.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.lslam_icp_match_clouds.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_icp_match_clouds_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_icp_debug_iteration.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_icp_stats.argtypes = [vp, vp]
     L.lslam_map_set_cloud.argtypes = [vp, vp, vp, i32, C.POINTER(HectorScan), C.POINTER(i32)]
     L.lslam_hector_process_many_deskewed.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp]

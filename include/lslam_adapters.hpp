@@ -837,6 +837,117 @@ class PlicpOdometryGpu {
   lslam_plicp_odom* h_ = nullptr;
 };
 
+// lesson2's ScanMatchICP (lesson2/src/scan_match_icp.cc) on the GPU: ScanCallback keeps the last scan and aligns its cloud
+// (the source) to the current scan's (the target), as ScanMatchWithICP (:135-164) does with a default-configured
+// pcl::IterativeClosestPoint; MatchPairs is the batch form.  Parity with the reference is unpinned (its arithmetic is PCL's);
+// the results are defined by tools/icp_cpu.py (see lslam_gpu.h).
+class ScanMatchICPGpu {
+ public:
+  // the LaserScan header fields ConvertScan2PointCloud reads; params NULL = PCL's defaults
+  ScanMatchICPGpu(lslam_context* ctx, double angleMin, double angleIncrement, double rangeMin, double rangeMax,
+                  const lslam_icp_params* params = nullptr)
+      : ctx_(ctx) {
+    lslam_icp_params p;
+    if (params) p = *params; else lslam_icp_params_defaults(&p);
+    check(lslam_icp_create(ctx, &p, &h_));
+    const int rc = lslam_icp_set_laser(h_, angleMin, angleIncrement, rangeMin, rangeMax);
+    if (rc != LSLAM_OK) {
+      lslam_icp_destroy(h_);
+      check(rc);
+    }
+  }
+  ~ScanMatchICPGpu() { lslam_icp_destroy(h_); }
+  ScanMatchICPGpu(const ScanMatchICPGpu&) = delete;
+  ScanMatchICPGpu& operator=(const ScanMatchICPGpu&) = delete;
+
+  // One scan of n beams.  The first scan only becomes the last one (false, *out zeroed: is_first_scan_, :56-62); afterwards
+  // *out is the transformation of the last scan's cloud onto this one's, and this scan becomes the last one.  The node prints
+  // the transformation only where out->converged is set (:148-163).  Every scan must have the first one's beam count.
+  bool ScanCallback(const float* ranges, int n, lslam_icp_record* out) {
+    std::memset(out, 0, sizeof *out);
+    if (n < 0 || !ranges) throw std::invalid_argument("ScanMatchICPGpu::ScanCallback: a scan is required");
+    if (!initialized_) {
+      last_.assign(ranges, ranges + n);
+      initialized_ = true;
+      return false;
+    }
+    if ((int)last_.size() != n) throw std::invalid_argument("ScanMatchICPGpu::ScanCallback: the beam count changed");
+    ScanMatchWithICP(ranges, n, out);
+    last_.assign(ranges, ranges + n);
+    return true;
+  }
+  // last -> current (:135-164)
+  void ScanMatchWithICP(const float* ranges, int n, lslam_icp_record* out) {
+    two_.resize(2 * (size_t)n);
+    std::memcpy(two_.data(), last_.data(), (size_t)n * sizeof(float));
+    std::memcpy(two_.data() + n, ranges, (size_t)n * sizeof(float));
+    const int32_t source = 0, target = 1;
+    check(lslam_icp_match_batch(h_, 2, n, two_.data(), n, 1, &source, &target, nullptr, out));
+  }
+  // nPairs pairs over nScans scans (row k at ranges + k * rangesStride): pair b aligns scan pairSource[b] to scan
+  // pairTarget[b]; firstGuess (nPairs x 3: x, y, yaw) may be NULL
+  void MatchPairs(int nScans, int nReadings, const float* ranges, int rangesStride, int nPairs, const int32_t* pairSource,
+                  const int32_t* pairTarget, const double* firstGuess, lslam_icp_record* out) {
+    check(lslam_icp_match_batch(h_, nScans, nReadings, ranges, rangesStride, nPairs, pairSource, pairTarget, firstGuess, out));
+  }
+  // every scan's cloud onto the next one's: out has nScans - 1 records
+  void MatchConsecutive(int nScans, int nReadings, const float* ranges, int rangesStride, lslam_icp_record* out) {
+    if (nScans < 2) return;
+    idx_.resize((size_t)nScans);
+    for (int k = 0; k < nScans; k++) idx_[k] = k;
+    MatchPairs(nScans, nReadings, ranges, rangesStride, nScans - 1, idx_.data(), idx_.data() + 1, nullptr, out);
+  }
+  // {pairs matched, kernel launches, buffer growths, host waits}
+  void stats(int64_t out[4]) const { lslam_icp_stats(h_, out); }
+  lslam_icp* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_icp* h_ = nullptr;
+  bool initialized_ = false;
+  std::vector<float> last_, two_;
+  std::vector<int32_t> idx_;
+};
+
+// lesson2's ScanToPointCloud2Converter (lesson2/src/scan_to_pointclod2_converter.cc) on the GPU: ScanCallback (:44-92) turns a
+// scan into n points (x, y, z) of float32, an invalid reading into the node's invalid_point_ (NaN, NaN, NaN).
+class ScanToPointCloud2ConverterGpu {
+ public:
+  ScanToPointCloud2ConverterGpu(lslam_context* ctx, double angleMin, double angleIncrement, double rangeMin, double rangeMax)
+      : ctx_(ctx) {
+    lslam_icp_params p;
+    lslam_icp_params_defaults(&p);
+    p.invalid_as_nan = 1;
+    check(lslam_icp_create(ctx, &p, &h_));
+    const int rc = lslam_icp_set_laser(h_, angleMin, angleIncrement, rangeMin, rangeMax);
+    if (rc != LSLAM_OK) {
+      lslam_icp_destroy(h_);
+      check(rc);
+    }
+  }
+  ~ScanToPointCloud2ConverterGpu() { lslam_icp_destroy(h_); }
+  ScanToPointCloud2ConverterGpu(const ScanToPointCloud2ConverterGpu&) = delete;
+  ScanToPointCloud2ConverterGpu& operator=(const ScanToPointCloud2ConverterGpu&) = delete;
+
+  // one scan: xyz = n x 3 floats, valid = n bytes
+  void ScanCallback(const float* ranges, int n, float* xyz, uint8_t* valid) { ConvertMany(1, n, ranges, n, xyz, valid); }
+  // nScans scans in one launch (row k at ranges + k * rangesStride)
+  void ConvertMany(int nScans, int nReadings, const float* ranges, int rangesStride, float* xyz, uint8_t* valid) {
+    check(lslam_icp_convert_batch(h_, nScans, nReadings, ranges, rangesStride, xyz, valid));
+  }
+  lslam_icp* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  lslam_icp* h_ = nullptr;
+};
+
 // gmapping::ScanMatcherMap (lesson4/include/lesson4/gmapping/grid/map.h) on the GPU, read side, plus the node's
 // ComputeMap (gmapping.cc:171-242).  cell() reads from a host copy of the counters, refreshed after every change.
 struct IntPoint2 {  // gmapping::IntPoint

@@ -1234,6 +1234,105 @@ int lslam_plicp_odom_process_many(lslam_plicp_odom* h, int n_steps, int n_readin
 /* out = {scans processed, kernel launches, buffer growths, host waits} */
 int lslam_plicp_odom_stats(const lslam_plicp_odom* h, int64_t out[4]);
 
+/* ---------------------------------------------------------------------------------------- */
+/* lesson2 point-to-point ICP pair matching (ScanMatchICP: lesson2/src/scan_match_icp.cc, and */
+/* the cloud of lesson2/src/scan_to_pointclod2_converter.cc, "C/" below), many pairs per      */
+/* launch.                                                                                    */
+/* STANDING: PARITY WITH THE REFERENCE IS UNPINNED.  Its arithmetic lives in PCL              */
+/* (IterativeClosestPoint, with FLANN and Eigen under it), which is neither vendored nor       */
+/* pinned.  The results are DEFINED by this project's own fp64 restatement of PCL 1.8's        */
+/* computeTransformation with DefaultConvergenceCriteria: `icp` in tools/icp_cpu.py.  All      */
+/* device arithmetic is fp64 on the stored float32 x, y; z is ignored.                         */
+/* Five deliberate rules:                                                                     */
+/*  1. LOWEST INDEX: among equal distances the lowest target index wins (FLANN's order among   */
+/*     equals is unspecified).                                                                */
+/*  2. FP64 ON THE ORIGINAL POINTS: every iteration transforms the original source points by   */
+/*     the accumulated transform, where PCL re-transforms a float cloud in place.              */
+/*  3. 2-D CLOSED FORM: theta = atan2(Sxy - Syx, Sxx + Syy), t = qbar - R(theta) pbar from the  */
+/*     means and then the centred sums of the accepted pairs, where PCL runs a 3-D SVD.        */
+/*  4. LITERAL ORIGIN POINTS: an invalid reading stays in the cloud as the point (0, 0, 0), as */
+/*     the node leaves it (scan_match_icp.cc:96-123), and is matched like any other point.     */
+/*  5. skip_invalid = 1 is the opt-in that removes the invalid readings from both clouds.  A   */
+/*     point whose x or y is not finite (C/'s NaN point) never takes part, in either mode.     */
+/* And a fact about the definition: THE ORDER OF THE SUMS is part of it -- 256 partial sums     */
+/* over the points l, l + 256, ... in ascending index, a binary tree per 64 partials, the four  */
+/* groups in order (tools/icp_cpu.py block_sum).  With transformation_epsilon = 0 rule 2 below  */
+/* fires only on an increment that is exactly the identity, which at a fixed point is decided  */
+/* by the last bit of these sums.                                             */
+/* ---------------------------------------------------------------------------------------- */
+#define LSLAM_ICP_MAX_POINTS 2048
+/* defaults = what lesson2 leaves in place, PCL's own */
+typedef struct lslam_icp_params {
+  double max_correspondence_distance; /* sqrt(DBL_MAX); a correspondence is accepted iff d2 <= its square */
+  double transformation_epsilon;      /* 0 */
+  double euclidean_fitness_epsilon;   /* -DBL_MAX */
+  double absolute_mse;                /* 1e-12 */
+  int32_t max_iterations;             /* 10; at least 1 */
+  int32_t skip_invalid;               /* 0 */
+  int32_t invalid_as_nan;             /* 0; 1: the conversion writes C/'s invalid_point_ (NaN, NaN, NaN) for an invalid reading */
+  int32_t reserved;
+} lslam_icp_params; /* 48 bytes */
+void lslam_icp_params_defaults(lslam_icp_params* p);
+/* state: the stop rule that fired -- 1 iterations >= max_iterations, 2 cos(theta) >= 1 - transformation_epsilon and |t|^2 <=
+ * transformation_epsilon, 3 |mse - previous mse| < absolute_mse, 4 |mse - previous| / previous < euclidean_fitness_epsilon
+ * (converged = 1 for all four), 5 fewer than 3 correspondences were accepted (converged = 0, x = the pose accumulated so far). */
+typedef struct lslam_icp_record {
+  double x[3];        /* (tx, ty, atan2(s, c)) of the final transformation: source (pair_source) into target (pair_target) */
+  double fitness;     /* getFitnessScore(): mean over the source points of the squared distance from the finally transformed
+                         point to its nearest target point; DBL_MAX where no source point has one */
+  double mse;         /* mean accepted d2 of the last iteration's search, i.e. before its increment was applied */
+  int32_t converged;
+  int32_t iterations;
+  int32_t ncorr;      /* correspondences accepted by the last search */
+  int32_t state;
+  double reserved;
+} lslam_icp_record; /* 64 bytes */
+typedef struct lslam_icp lslam_icp;
+int lslam_icp_create(lslam_context* ctx, const lslam_icp_params* params, lslam_icp** out);
+void lslam_icp_destroy(lslam_icp* h);
+/* The LaserScan header fields, kept as float32 as the message keeps them: a reading is valid iff it is finite and
+ * range_min < r < range_max compared in float32; angle_i = angle_min + i * angle_increment evaluated in float32. */
+int lslam_icp_set_laser(lslam_icp* h, double angle_min, double angle_increment, double range_min, double range_max);
+/* ConvertScan2PointCloud (scan_match_icp.cc:89-130) for n_scans scans in one launch.  ranges: n_scans rows of n_readings float32,
+ * row k at ranges + k * ranges_stride.  out_xyz: n_scans x n_readings x 3 float32, x = (float)((double)r * cos((double)angle)),
+ * y with sin, z = 0; an invalid reading gives (0, 0, 0), or (NaN, NaN, NaN) with invalid_as_nan.  out_valid: n_scans x n_readings
+ * bytes, produced in both modes.  This is the layout lslam_deskew_batch writes and lslam_map_set_cloud reads.  The _dev form
+ * takes all three in HBM and makes no host wait. */
+int lslam_icp_convert_batch(lslam_icp* h, int n_scans, int n_readings, const float* ranges, int ranges_stride, float* out_xyz,
+                            uint8_t* out_valid);
+int lslam_icp_convert_batch_dev(lslam_icp* h, int n_scans, int n_readings, const float* ranges_dev, int ranges_stride,
+                                float* out_xyz_dev, uint8_t* out_valid_dev);
+/* ScanMatchWithICP (scan_match_icp.cc:135-164) for n_pairs pairs: one conversion launch and ONE match launch (a workgroup per
+ * pair, the iterations loop on the device).  Pair b aligns the cloud of scan pair_source[b] to the cloud of scan pair_target[b]
+ * (the node: source = last, target = current).  first_guess: n_pairs x 3 doubles (x, y, yaw), NULL = zeros.  pair_source /
+ * pair_target are HOST arrays in both forms.  The host form owns its buffers (a repeated shape allocates nothing) and waits
+ * once, at its end.  The _dev form takes ranges, first_guess and out in HBM, is asynchronous on lslam_stream() and makes no host
+ * wait, with the back-pressure of lslam_plicp_match_batch_dev: the pair indices go up through a ring of 4 pinned slots.
+ * A pair's record is byte for byte the same alone and in any batch.  n_pairs == 0 is LSLAM_OK and launches nothing.
+ * LSLAM_ERR_INVALID_ARGUMENT, outputs untouched: NULL pointers, a pair index outside [0, n_scans), no laser set.
+ * LSLAM_ERR_UNSUPPORTED: more than LSLAM_ICP_MAX_POINTS readings. */
+int lslam_icp_match_batch(lslam_icp* h, int n_scans, int n_readings, const float* ranges, int ranges_stride, int n_pairs,
+                          const int32_t* pair_source, const int32_t* pair_target, const double* first_guess, lslam_icp_record* out);
+int lslam_icp_match_batch_dev(lslam_icp* h, int n_scans, int n_readings, const float* ranges_dev, int ranges_stride, int n_pairs,
+                              const int32_t* pair_source, const int32_t* pair_target, const double* first_guess_dev,
+                              lslam_icp_record* out_dev);
+/* The same on clouds: xyz = n_clouds x n_points x 3 float32, valid = n_clouds x n_points bytes or NULL (all valid; read only with
+ * skip_invalid) -- a converter's or the de-skew's output.  ONE launch; needs no laser. */
+int lslam_icp_match_clouds(lslam_icp* h, int n_clouds, int n_points, const float* xyz, const uint8_t* valid, int n_pairs,
+                           const int32_t* pair_source, const int32_t* pair_target, const double* first_guess, lslam_icp_record* out);
+int lslam_icp_match_clouds_dev(lslam_icp* h, int n_clouds, int n_points, const float* xyz_dev, const uint8_t* valid_dev, int n_pairs,
+                               const int32_t* pair_source, const int32_t* pair_target, const double* first_guess_dev,
+                               lslam_icp_record* out_dev);
+/* ONE iteration from x_in = (x, y, yaw), by the same device code as the batch kernel (host pointers; one launch, one wait).
+ * Per source point: corr = the target index, -1 where the correspondence was rejected or the point is masked; d2 = the best
+ * squared distance (+inf where there is none).  inc = the solved increment (tx, ty, theta), NaN where fewer than 3 were accepted;
+ * mse and ncorr of this search.  src_valid / tgt_valid may be NULL. */
+int lslam_icp_debug_iteration(lslam_icp* h, const float* src_xyz, const float* tgt_xyz, const uint8_t* src_valid,
+                              const uint8_t* tgt_valid, int n, const double x_in[3], int32_t* corr, double* d2, double inc[3],
+                              double* mse, int32_t* ncorr);
+/* out = {pairs matched, kernel launches, buffer growths (device or pinned), host waits} */
+int lslam_icp_stats(const lslam_icp* h, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
