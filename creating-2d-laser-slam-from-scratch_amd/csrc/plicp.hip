@@ -17,7 +17,7 @@
 //      distance at rank ridx), because the trimmed list is a prefix of the sorted one.
 //   5. the ten sums of A^T A and the four of A^T b, a fixed shuffle tree and a fixed order over the waves, so a pair's
 //      record does not depend on the batch it is in; the closed-form solve (every lane does the same arithmetic on the same
-//      sums: no hand-over): the 2x2 eigen-decomposition, every real root of the helper's quartic in lambda -- bracketed
+//      sums: no hand-over): the 2x2 eigen-decomposition, every real root of the Lagrange quartic in lambda -- bracketed
 //      between the quartic's critical points and bisected down to neighbouring doubles -- and the lowest-cost root.
 // The loops are bounded by the beam count and by 128 bisection steps: no spins, no hand-overs between blocks, no scratch.
 #include <cmath>
@@ -161,28 +161,34 @@ __device__ bool pl_solve(const double* m, const double* atb, double* sol) {
   const double e0 = mean - rad, e1 = mean + rad;
   const double hp0 = -s * h0 + c * h1, hp1 = c * h0 + s * h1;
   const double P0 = hp0 * hp0, P1 = hp1 * hp1;
-  // The quartic in L is the HELPER'S, coefficient for coefficient: numpy multiplies a float64 scalar into a poly1d element by
-  // element, so what _solve_point_to_line hands to np.roots is
-  //     (2L + 2e0)^2 (2L + 2e1)^2 - 4 (hp0^2 + hp1^2) L - 4 (hp0^2 e1^2 + hp1^2 e0^2)
-  // and not the Lagrange condition's hp0^2 (2L + 2e1)^2 + hp1^2 (2L + 2e0)^2 on the right.  The results are defined by the
-  // helper, so this is the polynomial solved here.  With y = L + mean and over 16:  f(y) = (y^2 - r^2)^2 - a (y - mean) - b.
-  // Its real roots lie between the critical points, which lie between the turning points +-r/sqrt(3) of f'.
+  // The quartic in L is the Lagrange condition of the cost: |u| = 1 with u_i = -hp_i / (2 e_i + 2 L), that is
+  //     (2L + 2e0)^2 (2L + 2e1)^2 = hp0^2 (2L + 2e1)^2 + hp1^2 (2L + 2e0)^2.
+  // With y = L + mean and over 16:  f(y) = (y^2 - r^2)^2 - (P0 (y + r)^2 + P1 (y - r)^2) / 4, whose derivative is the
+  // depressed cubic f'(y) = 4 y^3 - (4 r^2 + (P0 + P1) / 2) y - (P0 - P1) r / 2.
+  // The real roots of f lie between its critical points, which lie between the turning points +-k of f'.  The constant term
+  // of f' takes either sign, so a lone critical point lies on either side: three of them when f'(-k) > 0 > f'(k); one below
+  // -k when f'(k) >= 0 (then f' > 0 from -k on); one above k otherwise (then f' <= 0 up to k).  (|(P0 - P1) r / 2| <= 8 k^3
+  // whatever P0, P1 >= 0 and r are, with equality at P = 16 r^2 on one side alone: the lone cases are that tangency and
+  // its rounding, on either side.)
   // A root is taken where f changes sign.  A tangent (double) root changes none and is not seen, where np.roots returns it as a
   // pair the helper may accept (|imag| <= 1e-9 max(1, |re|)) and evaluate: on such an input -- none is known -- the device can
   // choose another root than the helper, or none (the zero result).
   const double r2 = rad * rad;
-  const double qa = 0.25 * (P0 + P1), qb = 0.25 * (P0 * (e1 * e1) + P1 * (e0 * e0));
-  auto f = [&](double y) { return ((y * y - r2) * (y * y - r2) - qa * (y - mean)) - qb; };
-  auto fd = [&](double y) { return (4.0 * y * y * y - 4.0 * r2 * y) - qa; };
-  const double c0 = r2 * r2 + qa * mean - qb;
-  const double R = 2.0 * fmax(fmax(sqrt(2.0 * r2), cbrt(fabs(qa))), sqrt(sqrt(fabs(c0)))) + 1e-300;  // Fujiwara's bound
-  const double k3 = rad / sqrt(3.0);
-  double c1 = -R, c2 = -R;  // (without them the first two intervals are empty)
-  if (fd(-k3) > 0.0) {
-    c1 = pl_bisect(fd, -R, -k3, false);
-    c2 = pl_bisect(fd, -k3, k3, true);
-  }
-  const double edge[5] = {-R, c1, c2, pl_bisect(fd, k3, R, false), R};
+  const double qs = 0.25 * (P0 + P1), qd = 0.5 * (P0 - P1) * rad;
+  auto f = [&](double y) {
+    const double w = y * y - r2;
+    return w * w - 0.25 * (P0 * ((y + rad) * (y + rad)) + P1 * ((y - rad) * (y - rad)));
+  };
+  auto fd = [&](double y) { return (4.0 * y * y * y - (4.0 * r2 + 2.0 * qs) * y) - qd; };
+  // Fujiwara's bound on y^4 + a2 y^2 + a1 y + a0:  a2 = -(2 r^2 + qs), a1 = -qd, a0 = r^4 - qs r^2
+  const double R = 2.0 * fmax(fmax(sqrt(2.0 * r2 + qs), cbrt(fabs(qd))), sqrt(sqrt(fabs(r2 * (r2 - qs))))) + 1e-300;
+  const double k3 = sqrt((4.0 * r2 + 2.0 * qs) / 12.0);
+  // the critical points in ascending order; an absent one repeats its neighbour, which leaves its interval empty
+  const bool below = fd(k3) >= 0.0, three = !below && fd(-k3) > 0.0;
+  const double c1 = (three || below) ? pl_bisect(fd, -R, -k3, false) : -R;
+  const double c2 = three ? pl_bisect(fd, -k3, k3, true) : c1;
+  const double c3 = below ? c2 : pl_bisect(fd, k3, R, false);
+  const double edge[5] = {-R, c1, c2, c3, R};
   bool have = false;
   double bcost = 0.0, bu0 = 0.0, bu1 = 0.0;
 #pragma unroll

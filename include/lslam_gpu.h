@@ -1128,11 +1128,12 @@ int lslam_features_stats(const lslam_features* f, int64_t out[4]);
 /*  3. LITERAL PREDICTION: GetPrediction (O/:442-456) reads linear.y and linear.z, which        */
 /*     nothing ever sets, so the prediction is (v.linear.x < 1e-6 ? 0 : dt * v.linear.x, 0, 0): */
 /*     no angular prediction, and a negative speed predicts nothing.                           */
-/*  4. THE HELPER'S QUARTIC: the polynomial in lambda that sm_icp's solve hands to np.roots is   */
-/*     (2L+2e0)^2 (2L+2e1)^2 - 4 (hp0^2+hp1^2) L - 4 (hp0^2 e1^2 + hp1^2 e0^2) -- numpy multiplies */
-/*     a float64 scalar into a poly1d element by element -- and not the Lagrange condition of    */
-/*     the paper.  The helper defines the results, so this is the polynomial solved here: all    */
-/*     its real roots, the lowest-cost one.                                     */
+/*  4. THE QUARTIC IS THE LAGRANGE CONDITION of the stated cost: with t eliminated the cost is     */
+/*     u^T S u + h^T u on |u| = 1, and in S's eigenbasis (2L+2e0)^2 (2L+2e1)^2 =                  */
+/*     hp0^2 (2L+2e1)^2 + hp1^2 (2L+2e0)^2.  All its real roots are tried and the lowest-cost    */
+/*     one taken: the solve is the minimum of sum_k (n_k . (R(theta) p_k + t - q_k))^2, held to   */
+/*     an independent search of that cost by the tests.  It has no unique answer for 3 or 4      */
+/*     correspondences or a scene of exactly two lines.                         */
 /* ---------------------------------------------------------------------------------------- */
 #define LSLAM_PLICP_MAX_READINGS 2048
 /* the sm_params sm_icp reads; defaults = ScanMatchPLICP::InitParams (scan_match_plicp.cc:43-156) */

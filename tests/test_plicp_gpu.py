@@ -3,9 +3,10 @@ restatement (tests/plicp_restatement.py) on the scenarios of tests/plicp_cases.p
 reading by reading, the solved pose, the full runs, and the batch forms byte for byte.
 
 Bounds.  x of one iteration (debug_iteration) against the restatement: measured max |device - restatement| over the cases
-5.4e-13 (the sums are taken in another order, the 2x2 eigen-decomposition and the roots by other routes), allowed 8 x that,
-as the solve's conditioning varies with the geometry; never above 1e-7.  Full runs: the project's contract, 1e-4 m / 1e-4 rad
-(measured 1.8e-12, on a 65-reading pair; 2e-14 on the full scans).  Known motions: 1e-6 m / 1e-6 rad, what tests/test_plicp.py holds the CPU helper to."""
+5.4e-13 (beam_counts_65; the sums are taken in another order, the 2x2 eigen-decomposition and the roots by other routes),
+allowed 8 x that, as the solve's conditioning varies with the geometry; never above 1e-7.  Full runs: the project's contract,
+1e-4 m / 1e-4 rad (measured 2.0e-13, on a 63-reading pair; 2.1e-14 on the full scans).  Known motions: 1e-6 m / 1e-6 rad, what
+tests/test_plicp.py holds the CPU helper to."""
 import math
 
 import numpy as np

@@ -79,13 +79,9 @@ def laser_scan_to_ldp(ranges, angle_min: float, angle_increment: float, range_mi
     return Ldp(valid.astype(np.int8), np.where(valid, r, -1.0), theta, float(theta[0]), float(theta[-1]))
 
 
-def _solve_point_to_line(p: np.ndarray, q: np.ndarray, nrm: np.ndarray):
-    """min over (t, theta) of sum_k (n_k . (R(theta) p_k + t - q_k))^2, closed form.
-
-    With x = [tx, ty, c, s] and rows a_k = [nx, ny, n.p, n.(-py, px)] the cost is |A x - b|^2 subject to
-    c^2 + s^2 = 1.  Eliminating t leaves a 2x2 problem u^T S u + h^T u with |u| = 1, solved through the
-    Lagrange condition (2S + 2 lambda I) u = -h: a quartic in lambda in S's eigenbasis.
-    """
+def _reduce_point_to_line(p: np.ndarray, q: np.ndarray, nrm: np.ndarray):
+    """The point-to-line cost with t eliminated, u^T s2 u + h^T u, and s2's eigenbasis -> (ainv, bb, g, s2, h, e, v, hp);
+    None where the normals do not span the plane."""
     a = np.stack([nrm[:, 0], nrm[:, 1], nrm[:, 0] * p[:, 0] + nrm[:, 1] * p[:, 1],
                   -nrm[:, 0] * p[:, 1] + nrm[:, 1] * p[:, 0]], axis=1)
     b = nrm[:, 0] * q[:, 0] + nrm[:, 1] * q[:, 1]
@@ -99,10 +95,28 @@ def _solve_point_to_line(p: np.ndarray, q: np.ndarray, nrm: np.ndarray):
     h = g[2:] - bb.T @ ainv @ g[:2]
     e, v = np.linalg.eigh(s2)
     hp = v.T @ h
-    # hp0^2 (2 e1 + 2 L)^2 + hp1^2 (2 e0 + 2 L)^2 = (2 e0 + 2 L)^2 (2 e1 + 2 L)^2
+    return ainv, bb, g, s2, h, e, v, hp
+
+
+def _solve_point_to_line(p: np.ndarray, q: np.ndarray, nrm: np.ndarray):
+    """min over (t, theta) of sum_k (n_k . (R(theta) p_k + t - q_k))^2, closed form.
+
+    With x = [tx, ty, c, s] and rows a_k = [nx, ny, n.p, n.(-py, px)] the cost is |A x - b|^2 subject to
+    c^2 + s^2 = 1.  Eliminating t leaves a 2x2 problem u^T S u + h^T u with |u| = 1, solved through the
+    Lagrange condition (2S + 2 lambda I) u = -h: a quartic in lambda in S's eigenbasis.  Its real roots are the
+    stationary points of the cost on the circle and the lowest-cost one is the minimum
+    (tests/test_plicp_solve_oracle.py holds the result to an independent search of the cost).
+    """
+    red = _reduce_point_to_line(p, q, nrm)
+    if red is None:
+        return None
+    ainv, bb, g, s2, h, e, v, hp = red
+    # |u| = 1 with u_i = -hp_i / (2 e_i + 2 L):  hp0^2 (2 e1 + 2 L)^2 + hp1^2 (2 e0 + 2 L)^2 = (2 e0 + 2 L)^2 (2 e1 + 2 L)^2.
+    # The scalars stand on the RIGHT of the poly1d: numpy multiplies a float64 scalar on the left into a poly1d element by
+    # element and returns an array of coefficients, not the scaled polynomial.
     p0 = np.poly1d([2.0, 2.0 * e[0]])
     p1 = np.poly1d([2.0, 2.0 * e[1]])
-    poly = p0 * p0 * p1 * p1 - hp[0] ** 2 * p1 * p1 - hp[1] ** 2 * p0 * p0
+    poly = p0 * p0 * p1 * p1 - p1 * p1 * float(hp[0] ** 2) - p0 * p0 * float(hp[1] ** 2)
     best = None
     for lam in np.roots(poly.coeffs):
         if abs(lam.imag) > 1e-9 * max(1.0, abs(lam.real)):
