@@ -237,6 +237,115 @@ class Deskewer:
         return dict(zip(("scans", "launches", "growths", "host_waits"), (int(v) for v in out)))
 
 
+MSYNC_QUEUED, MSYNC_CORRECTED, MSYNC_WAIT_IMU, MSYNC_WAIT_ODOM, MSYNC_IMU_NO_LEAD_SAMPLE, MSYNC_IMU_OVERFLOW = 0, 1, -1, -2, -3, -4
+MSYNC_QUEUE_LENGTH = 2000  # LSLAM_MSYNC_QUEUE_LENGTH
+MSYNC_RECORD = np.dtype([("status", np.int32), ("n_imu", np.int32), ("scan_time_start", np.float64), ("time_increment", np.float64),
+                         ("start_odom_time", np.float64), ("end_odom_time", np.float64), ("odom_incre", np.float32, (3,)),
+                         ("pad", np.float32), ("imu_front", np.int64), ("odom_front", np.int64), ("start_odom_index", np.int64),
+                         ("end_odom_index", np.int64)])  # lslam_msync_record
+
+
+class MsyncLaser(C.Structure):
+    _fields_ = [("angle_min", C.c_float), ("angle_increment", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float)]
+
+
+class MotionSync:
+    """lslam_msync: lesson5's node from its callbacks on -- IMU, odometry and LaserScan messages in, de-skewed clouds out.  The
+    queues, their fronts, the sticky start / end odometry messages and the one queued scan live on the device; `deskewer` (a
+    Deskewer of the same context, made here when None) runs the back half."""
+
+    def __init__(self, ctx: "Context", use_imu: bool = True, use_odom: bool = True, deskewer: "Deskewer | None" = None):
+        self.ctx, self.L = ctx, ctx.L
+        self.deskewer = deskewer if deskewer is not None else Deskewer(ctx)
+        h = C.c_void_p()
+        ctx.check(self.L.lslam_msync_create(ctx.h, int(use_imu), int(use_odom), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_msync_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.ctx.check(self.L.lslam_msync_reset(self.h))
+
+    def push_imu(self, stamps, gyro_xyz):
+        """n ImuCallbacks: stamps [n], gyro_xyz [n, 3] (angular_velocity)."""
+        t = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        w = np.ascontiguousarray(gyro_xyz, np.float64).reshape(len(t), 3)
+        self.ctx.check(self.L.lslam_msync_push_imu(self.h, len(t), t.ctypes.data, w.ctypes.data))
+
+    def push_odom(self, stamps, pos_xyz, quat_xyzw):
+        """n OdomCallbacks: stamps [n], pos_xyz [n, 3], quat_xyzw [n, 4]."""
+        t = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        p = np.ascontiguousarray(pos_xyz, np.float64).reshape(len(t), 3)
+        q = np.ascontiguousarray(quat_xyzw, np.float64).reshape(len(t), 4)
+        self.ctx.check(self.L.lslam_msync_push_odom(self.h, len(t), t.ctypes.data, p.ctypes.data, q.ctypes.data))
+
+    @staticmethod
+    def _small(laser, stamps, time_increments, imu_seen, odom_seen):
+        hdr = laser if isinstance(laser, MsyncLaser) else MsyncLaser(*[float(v) for v in laser])
+        t = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        ti = np.ascontiguousarray(time_increments, np.float32).reshape(-1)
+        if len(ti) != len(t):
+            raise ValueError("one time_increment per scan message")
+        seen = [None if a is None else np.ascontiguousarray(a, np.int64).reshape(len(t)) for a in (imu_seen, odom_seen)]
+        return hdr, t, ti, seen
+
+    def scans(self, laser, ranges, stamps, time_increments, imu_seen=None, odom_seen=None, n_readings=None):
+        """n ScanCallbacks.  laser: (angle_min, angle_increment, range_min, range_max); ranges [n, stride] float32 ->
+        (xyz [n, n_readings, 3] float32, valid [n, n_readings] bool, records [n] MSYNC_RECORD).  Row k is the cloud of message
+        k - 1 (row 0: the scan the previous call left queued); rows of queued or refused callbacks are zeros."""
+        hdr, t, ti, seen = self._small(laser, stamps, time_increments, imu_seen, odom_seen)
+        n = len(t)
+        r = np.ascontiguousarray(ranges, dtype=np.float32).reshape(n, -1) if n else np.zeros((0, 0), np.float32)
+        stride = r.shape[1]
+        nr = stride if n_readings is None else int(n_readings)
+        xyz = np.zeros((n, nr, 3), np.float32)
+        valid = np.zeros((n, nr), np.uint8)
+        rec = np.zeros(n, MSYNC_RECORD)
+        self.ctx.check(self.L.lslam_msync_scans(self.h, self.deskewer.h, C.byref(hdr), n, nr, r.ctypes.data, stride, t.ctypes.data,
+                                                ti.ctypes.data, None if seen[0] is None else seen[0].ctypes.data,
+                                                None if seen[1] is None else seen[1].ctypes.data, xyz.ctypes.data,
+                                                valid.ctypes.data, rec.ctypes.data))
+        return xyz, valid.astype(bool), rec
+
+    def scans_dev(self, laser, n_readings: int, ranges_ptr: int, ranges_stride: int, stamps, time_increments, xyz_ptr: int,
+                  valid_ptr: int, records_ptr=None, imu_seen=None, odom_seen=None):
+        """The same with ranges, xyz (float32), valid (uint8) and records (MSYNC_RECORD, may be None) in HBM: asynchronous on
+        the context's stream, no host wait."""
+        hdr, t, ti, seen = self._small(laser, stamps, time_increments, imu_seen, odom_seen)
+        self.ctx.check(self.L.lslam_msync_scans_dev(self.h, self.deskewer.h, C.byref(hdr), len(t), n_readings, ranges_ptr,
+                                                    ranges_stride, t.ctypes.data, ti.ctypes.data,
+                                                    None if seen[0] is None else seen[0].ctypes.data,
+                                                    None if seen[1] is None else seen[1].ctypes.data, xyz_ptr, valid_ptr,
+                                                    records_ptr))
+
+    def read_windows(self, n_msgs: int):
+        """The last call's integrated IMU samples -> (imu_first [n_msgs + 1], imu_time [T], imu_rot [T, 3]).  Waits."""
+        first = np.zeros(n_msgs + 1, np.int32)
+        self.ctx.check(self.L.lslam_msync_read_windows(self.h, first.ctypes.data, None, None, 0))
+        total = int(first[-1])
+        t, rot = np.zeros(max(total, 1), np.float64), np.zeros((max(total, 1), 3), np.float64)
+        if total:
+            self.ctx.check(self.L.lslam_msync_read_windows(self.h, first.ctypes.data, t.ctypes.data, rot.ctypes.data, total))
+        return first, t[:total], rot[:total]
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 6)()
+        self.ctx.check(self.L.lslam_msync_stats(self.h, out))
+        return dict(zip(("callbacks", "corrected", "refused", "launches", "growths", "host_waits"), (int(v) for v in out)))
+
+
 FEATURE_SECTORS, FEATURE_PICKS, FEATURE_MAX_READINGS = 6, 20, 1500  # LSLAM_FEATURE_*
 FEATURE_RECORD = np.dtype([("n_valid", np.int32), ("n_corners", np.int32), ("per_sector", np.int32, (6,))])  # lslam_feature_record
 
@@ -838,6 +947,16 @@ def lib() -> C.CDLL:
     L.lslam_deskew_stats.argtypes = [vp, vp]
     L.lslam_deskew_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lslam_deskew_batch_dev.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_msync_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    L.lslam_msync_destroy.argtypes = [vp]
+    L.lslam_msync_destroy.restype = None
+    L.lslam_msync_reset.argtypes = [vp]
+    L.lslam_msync_push_imu.argtypes = [vp, i32, vp, vp]
+    L.lslam_msync_push_odom.argtypes = [vp, i32, vp, vp, vp]
+    L.lslam_msync_scans.argtypes = [vp, vp, C.POINTER(MsyncLaser), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_msync_scans_dev.argtypes = [vp, vp, C.POINTER(MsyncLaser), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_msync_read_windows.argtypes = [vp, vp, vp, vp, i32]
+    L.lslam_msync_stats.argtypes = [vp, vp]
     L.lslam_features_create.argtypes = [vp, C.POINTER(vp)]
     L.lslam_features_destroy.argtypes = [vp]
     L.lslam_features_destroy.restype = None

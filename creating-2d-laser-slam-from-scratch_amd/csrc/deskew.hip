@@ -10,54 +10,11 @@
 // (tests/test_deskew_pin.py: <= 4e-6 m, the device's float32 cos / sin being the difference).
 #include <cmath>
 
-#include "common.hpp"
+#include "deskew_impl.hpp"  // Aff3, get_transformation, inverse, mul; DeskewScan
 
 using namespace lslam;
 
 namespace {
-
-struct Aff3 {  // Eigen::Affine3f: linear (row-major here) + translation
-  float l[9], t[3];
-};
-
-// pcl::getTransformation(x, y, z, roll, pitch, yaw) for float
-__device__ __forceinline__ Aff3 get_transformation(float x, float y, float z, float roll, float pitch, float yaw) {
-  const float A = cosf(yaw), B = sinf(yaw), C = cosf(pitch), D = sinf(pitch), E = cosf(roll), F = sinf(roll);
-  const float DE = D * E, DF = D * F;
-  Aff3 t;
-  t.l[0] = A * C;  t.l[1] = A * DF - B * E;  t.l[2] = B * F + A * DE;  t.t[0] = x;
-  t.l[3] = B * C;  t.l[4] = A * E + B * DF;  t.l[5] = B * DE - A * F;  t.t[1] = y;
-  t.l[6] = -D;     t.l[7] = C * F;           t.l[8] = C * E;           t.t[2] = z;
-  return t;
-}
-__device__ __forceinline__ float cof3(const float* m, int i, int j) {  // Eigen cofactor_3x3<i,j>
-  const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-  return m[3 * i1 + j1] * m[3 * i2 + j2] - m[3 * i1 + j2] * m[3 * i2 + j1];
-}
-// Transform::inverse(Affine): linear by the cofactor inverse (LU/InverseImpl.h), translation = (-Linv) * t
-__device__ __forceinline__ Aff3 inverse(const Aff3& a) {
-  const float* m = a.l;
-  const float c0 = cof3(m, 0, 0), c1 = cof3(m, 1, 0), c2 = cof3(m, 2, 0);
-  const float det = c0 * m[0] + (c1 * m[3] + c2 * m[6]);
-  const float invdet = 1.0f / det;
-  Aff3 r;
-  r.l[0] = c0 * invdet; r.l[1] = c1 * invdet; r.l[2] = c2 * invdet;
-  r.l[3] = cof3(m, 0, 1) * invdet; r.l[4] = cof3(m, 1, 1) * invdet; r.l[5] = cof3(m, 2, 1) * invdet;
-  r.l[6] = cof3(m, 0, 2) * invdet; r.l[7] = cof3(m, 1, 2) * invdet; r.l[8] = cof3(m, 2, 2) * invdet;
-  for (int i = 0; i < 3; i++)
-    r.t[i] = (-r.l[3 * i]) * a.t[0] + ((-r.l[3 * i + 1]) * a.t[1] + (-r.l[3 * i + 2]) * a.t[2]);
-  return r;
-}
-// Affine * Affine (Geometry/Transform.h): linear = L1 L2, translation = L1 t2 + t1; 3-term sums a0 + (a1 + a2)
-__device__ __forceinline__ Aff3 mul(const Aff3& a, const Aff3& b) {
-  Aff3 r;
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++)
-      r.l[3 * i + j] = a.l[3 * i] * b.l[j] + (a.l[3 * i + 1] * b.l[3 + j] + a.l[3 * i + 2] * b.l[6 + j]);
-    r.t[i] = (a.l[3 * i] * b.t[0] + (a.l[3 * i + 1] * b.t[1] + a.l[3 * i + 2] * b.t[2])) + a.t[i];
-  }
-  return r;
-}
 
 struct DeskewCfg {
   int n, n_imu_last;  // n_imu_last = current_imu_index_ (index of the last integrated IMU sample)
@@ -189,16 +146,6 @@ k_deskew(DeskewCfg c, const float* __restrict__ ranges, const double* __restrict
   __shared__ DeskewShared sh;
   deskew_body<false>(c, sh, ranges, imu_time, rx, ry, rz, nullptr, out_xyz, valid, 0, c.n);
 }
-
-// what differs from scan to scan of a batch (the geometry -- angles, range window, beam count -- is the call's)
-struct DeskewScan {
-  double t0, dt, odom_t0, odom_t1;
-  float odom_dx, odom_dy, odom_dz;
-  int use_imu, use_odom;
-  int imu_first, n_imu;  // its samples inside the call's concatenated IMU arrays
-  int pad;
-};
-static_assert(sizeof(DeskewScan) % 8 == 0, "the IMU doubles follow the scan records in one buffer");
 
 struct DeskewGeom {
   int n, ranges_stride;
@@ -373,32 +320,44 @@ int dsk_enqueue(lslam_deskew* d, int n_scans, int n_readings, const float* d_ran
   LSLAM_HIP(ctx, hipMemcpyAsync(d->d_meta.p, up_bytes, bytes, hipMemcpyHostToDevice, ctx->stream));
   LSLAM_HIP(ctx, hipEventRecord(d->slot_done[q], ctx->stream));
   d->slot_in_flight[q] = true;
-  // CreateAngleCache: once per geometry (a table of more beams serves a shorter scan of the same angles)
   const lslam_deskew_params& p0 = params[0];
-  if (n_readings > d->table_n || p0.angle_min != d->table_angle_min || p0.angle_increment != d->table_angle_inc) {
+  const float geom[4] = {p0.angle_min, p0.angle_increment, p0.range_min, p0.range_max};
+  return deskew_launch_records(d, n_scans, n_readings, d_ranges, ranges_stride, geom, (const DeskewScan*)d->d_meta.p,
+                               (const double*)(d->d_meta.p + rec_bytes), imu_total, d_xyz, d_valid);
+}
+
+}  // namespace
+
+int lslam::deskew_launch_records(lslam_deskew* d, int n_scans, int n_readings, const float* d_ranges, int ranges_stride,
+                                 const float geom[4], const DeskewScan* d_scans, const double* d_imu, int imu_total,
+                                 float* d_xyz, uint8_t* d_valid) {
+  lslam_context* ctx = d->ctx;
+  int rc;
+  // CreateAngleCache: once per geometry (a table of more beams serves a shorter scan of the same angles)
+  if (n_readings > d->table_n || geom[0] != d->table_angle_min || geom[1] != d->table_angle_inc) {
     rc = dsk_reserve(d, d->d_table, (size_t)n_readings);
     if (rc) return rc;
-    launch(ctx, "deskew_angles", k_deskew_angles, dim3((unsigned)((n_readings + 255) / 256)), dim3(256), 0, p0.angle_min,
-           p0.angle_increment, n_readings, d->d_table.p);
+    launch(ctx, "deskew_angles", k_deskew_angles, dim3((unsigned)((n_readings + 255) / 256)), dim3(256), 0, geom[0], geom[1],
+           n_readings, d->d_table.p);
     d->n_launches++;
     d->table_n = n_readings;
-    d->table_angle_min = p0.angle_min;
-    d->table_angle_inc = p0.angle_increment;
+    d->table_angle_min = geom[0];
+    d->table_angle_inc = geom[1];
   }
   DeskewGeom g;
   g.n = n_readings; g.ranges_stride = ranges_stride;
-  g.range_min = p0.range_min; g.range_max = p0.range_max;
-  g.angle_min = p0.angle_min; g.angle_inc = p0.angle_increment;
+  g.range_min = geom[2]; g.range_max = geom[3];
+  g.angle_min = geom[0]; g.angle_inc = geom[1];
   const dim3 grid((unsigned)((n_readings + kDeskewThreads - 1) / kDeskewThreads), (unsigned)n_scans);
-  launch(ctx, "deskew_batch", k_deskew_batch, grid, dim3(kDeskewThreads), 0, g, (const DeskewScan*)d->d_meta.p, d_ranges,
-         (const double*)(d->d_meta.p + rec_bytes), imu_total, (const double2*)d->d_table.p, d_xyz, d_valid);
+  launch(ctx, "deskew_batch", k_deskew_batch, grid, dim3(kDeskewThreads), 0, g, d_scans, d_ranges, d_imu, imu_total,
+         (const double2*)d->d_table.p, d_xyz, d_valid);
   d->n_launches++;
   d->n_scans += n_scans;
   LSLAM_HIP(ctx, hipGetLastError());
   return LSLAM_OK;
 }
 
-}  // namespace
+lslam_context* lslam::deskew_context(lslam_deskew* d) { return d->ctx; }
 
 extern "C" {
 

@@ -623,13 +623,21 @@ class HectorSlamFleetGpu {
 };
 
 // LidarUndistortion::CorrectLaserScan (lesson5/src/lidar_undistortion.cc:339-447) for many scans per launch.  The caller
-// keeps what the node's callbacks and Prune* steps produce -- per scan the header, the odometry increment and the
-// integrated IMU samples -- and hands a stretch of scans over at once; every scan's cloud is bit for bit what
-// lslam_deskew_scan returns for it.
+// of CorrectLaserScans* keeps what the node's callbacks and Prune* steps produce -- per scan the header, the odometry increment
+// and the integrated IMU samples -- and hands a stretch of scans over at once; every scan's cloud is bit for bit what
+// lslam_deskew_scan returns for it.  ImuCallback / OdomCallback / ScanCallback(s) are the whole node (:82-125): they keep
+// those too, on the device.
 class LidarUndistortionGpu {
  public:
-  explicit LidarUndistortionGpu(lslam_context* ctx) : ctx_(ctx) { check(lslam_deskew_create(ctx, &h_)); }
-  ~LidarUndistortionGpu() { lslam_deskew_destroy(h_); }
+  // useImu / useOdom: the node's parameters (:27-28); they matter to the callbacks below only
+  explicit LidarUndistortionGpu(lslam_context* ctx, bool useImu = true, bool useOdom = true)
+      : ctx_(ctx), use_imu_(useImu), use_odom_(useOdom) {
+    check(lslam_deskew_create(ctx, &h_));
+  }
+  ~LidarUndistortionGpu() {
+    lslam_msync_destroy(sync_);
+    lslam_deskew_destroy(h_);
+  }
   LidarUndistortionGpu(const LidarUndistortionGpu&) = delete;
   LidarUndistortionGpu& operator=(const LidarUndistortionGpu&) = delete;
 
@@ -654,12 +662,64 @@ class LidarUndistortionGpu {
   void stats(int64_t out[4]) const { lslam_deskew_stats(h_, out); }
   lslam_deskew* handle() { return h_; }
 
+  // ---- the node's own shape: raw messages in, de-skewed clouds out (lslam_msync; the queues, their fronts, the sticky
+  // start / end odometry messages and the one queued scan live on the device) ----
+  struct Clouds {
+    std::vector<float> xyz;                   // nMsgs x nReadings x 3; row k: the scan callback k corrected (message k - 1)
+    std::vector<uint8_t> valid;               // nMsgs x nReadings
+    std::vector<lslam_msync_record> records;  // nMsgs: status (LSLAM_MSYNC_*), times, odometry increment, fronts
+  };
+  // sensor_msgs/Imu: header.stamp and angular_velocity (:82-86)
+  void ImuCallback(double stamp, double wx, double wy, double wz) {
+    const double w[3] = {wx, wy, wz};
+    check(lslam_msync_push_imu(sync(), 1, &stamp, w));
+  }
+  void ImuCallbacks(int n, const double* stamps, const double* gyroXYZ) { check(lslam_msync_push_imu(sync(), n, stamps, gyroXYZ)); }
+  // nav_msgs/Odometry: header.stamp, pose.pose.position and orientation (x, y, z, w) (:89-93)
+  void OdomCallback(double stamp, const double posXYZ[3], const double quatXYZW[4]) {
+    check(lslam_msync_push_odom(sync(), 1, &stamp, posXYZ, quatXYZW));
+  }
+  void OdomCallbacks(int n, const double* stamps, const double* posXYZ, const double* quatXYZW) {
+    check(lslam_msync_push_odom(sync(), n, stamps, posXYZ, quatXYZW));
+  }
+  // One sensor_msgs/LaserScan (:96-125) with every message pushed so far in the queues.  Returns the record; outXYZ
+  // (nReadings x 3) and outValid (nReadings) hold the cloud of the PREVIOUS scan, zeros while the node queues or waits.
+  lslam_msync_record ScanCallback(const lslam_msync_laser& laser, int nReadings, const float* ranges, double stamp,
+                                  float timeIncrement, float* outXYZ, uint8_t* outValid) {
+    lslam_msync_record rec;
+    check(lslam_msync_scans(sync(), h_, &laser, 1, nReadings, ranges, nReadings, &stamp, &timeIncrement, nullptr, nullptr, outXYZ,
+                            outValid, &rec));
+    return rec;
+  }
+  // A stretch of LaserScans in one call.  imuSeen[k] / odomSeen[k]: how many IMU / odometry messages had arrived when scan
+  // callback k ran (NULL: all of them).
+  Clouds ScanCallbacks(const lslam_msync_laser& laser, int nMsgs, int nReadings, const float* ranges, int rangesStride,
+                       const double* stamps, const float* timeIncrements, const int64_t* imuSeen = nullptr,
+                       const int64_t* odomSeen = nullptr) {
+    Clouds out;
+    out.xyz.resize((size_t)nMsgs * nReadings * 3);
+    out.valid.resize((size_t)nMsgs * nReadings);
+    out.records.resize((size_t)nMsgs);
+    check(lslam_msync_scans(sync(), h_, &laser, nMsgs, nReadings, ranges, rangesStride, stamps, timeIncrements, imuSeen, odomSeen,
+                            out.xyz.data(), out.valid.data(), out.records.data()));
+    return out;
+  }
+  void Reset() { check(lslam_msync_reset(sync())); }
+  // {scan callbacks, scans corrected, scans refused, launches of the synchronisation's kernels, buffer growths, host waits}
+  void syncStats(int64_t out[6]) { check(lslam_msync_stats(sync(), out)); }
+
  private:
   void check(int rc) {
     if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
   }
+  lslam_msync* sync() {  // made by the first callback: CorrectLaserScans* alone needs none
+    if (!sync_) check(lslam_msync_create(ctx_, use_imu_, use_odom_, &sync_));
+    return sync_;
+  }
   lslam_context* ctx_;
+  bool use_imu_ = true, use_odom_ = true;
   lslam_deskew* h_ = nullptr;
+  lslam_msync* sync_ = nullptr;
 };
 
 // lesson1's LaserScan (lesson1/src/feature_detection.cc): ScanCallback's corner extraction, for one scan or many per

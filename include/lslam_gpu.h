@@ -986,6 +986,82 @@ int lslam_deskew_batch_dev(lslam_deskew* d, int n_scans, int n_readings, const f
 int lslam_deskew_stats(const lslam_deskew* d, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
+/* lesson5 IMU / odometry synchronisation: the FRONT half of LidarUndistortion::ScanCallback  */
+/* (lesson5/src/lidar_undistortion.cc:96-125) on the device, chained into the de-skew launch  */
+/* above.  Raw sensor_msgs/Imu, nav_msgs/Odometry and LaserScan messages go in, de-skewed      */
+/* clouds come out; the host stages no per-scan motion data.  The handle owns the node's state */
+/* in HBM: imu_queue_ and odom_queue_ (doubles), their fronts, start_odom_msg_ / end_odom_msg_ */
+/* as global message indices (-1: the default-constructed message, stamp 0, identity pose),    */
+/* the one LaserScan CacheLaserScan keeps queued, and scan_count_.                             */
+/* ---------------------------------------------------------------------------------------- */
+#define LSLAM_MSYNC_QUEUED 0              /* the first scan ever: only queued (:145-146) */
+#define LSLAM_MSYNC_CORRECTED 1
+#define LSLAM_MSYNC_WAIT_IMU (-1)         /* PruneImuDeque refused (:182-188, :199-200) */
+#define LSLAM_MSYNC_WAIT_ODOM (-2)        /* PruneOdomDeque refused (:257-263, :274-275) */
+#define LSLAM_MSYNC_IMU_NO_LEAD_SAMPLE (-3) /* a sample inside the scan and none before its start: :237 reads imu_time_[-1] */
+#define LSLAM_MSYNC_IMU_OVERFLOW (-4)     /* more than LSLAM_MSYNC_QUEUE_LENGTH integrated samples: past imu_time_'s end */
+#define LSLAM_MSYNC_QUEUE_LENGTH 2000     /* queueLength (:20) */
+/* One record per scan callback.  Callback k corrects the scan of callback k - 1 (CacheLaserScan's one-scan lag, :142-156);
+ * a scan that a Prune* step refuses has left laser_queue_ and is dropped, not retried, and IMU pops made before an odometry
+ * refusal stay made. */
+typedef struct lslam_msync_record {
+  int32_t status;                          /* LSLAM_MSYNC_* */
+  int32_t n_imu;                           /* current_imu_index_ + 1 (0: no sample in reach, corrected with zero rotation) */
+  double scan_time_start, time_increment;  /* of the scan this callback took off the queue (:154-155); 0 when QUEUED */
+  double start_odom_time, end_odom_time;   /* :301-302 */
+  float odom_incre[3], pad;                /* :332-334 */
+  int64_t imu_front, odom_front;           /* messages popped so far, after this callback (:191-197, :266-272) */
+  int64_t start_odom_index, end_odom_index;/* start_odom_msg_ / end_odom_msg_ after this callback, -1: the default message */
+} lslam_msync_record;
+typedef struct lslam_msync_laser {         /* the LaserScan header of the scans one call corrects */
+  float angle_min, angle_increment, range_min, range_max;
+} lslam_msync_laser;
+typedef struct lslam_msync lslam_msync;
+/* the node's constructor with its use_imu / use_odom parameters (:27-28); _reset brings the handle back to a fresh node
+ * (it waits for the stream; the buffers, and with them the growth and wait counts, are kept) */
+int lslam_msync_create(lslam_context* ctx, int use_imu, int use_odom, lslam_msync** out);
+void lslam_msync_destroy(lslam_msync* h);
+int lslam_msync_reset(lslam_msync* h);
+/* n ImuCallbacks (:82-86) / OdomCallbacks (:89-93): stamps[n], gyro_xyz[n][3] (angular_velocity), pos_xyz[n][3],
+ * quat_xyzw[n][4].  The messages are appended to the device queue by an asynchronous copy on lslam_stream(): no kernel, and
+ * no host wait unless the pinned staging area is still in flight (counted).  Messages a finished call has popped are
+ * discarded when room is needed; the buffers grow when they must (counted). */
+int lslam_msync_push_imu(lslam_msync* h, int n, const double* stamps, const double* gyro_xyz);
+int lslam_msync_push_odom(lslam_msync* h, int n, const double* stamps, const double* pos_xyz, const double* quat_xyzw);
+/* n_msgs ScanCallbacks (:96-125) in order.  ranges: row k at ranges + k * ranges_stride, stamps[k] = header.stamp,
+ * time_increments[k] the message's float32 field.  imu_seen[k] / odom_seen[k]: how many IMU / odometry messages, counted
+ * since create or reset, had arrived when callback k ran -- the interleaving of the callbacks; non-decreasing, also across
+ * calls, and at most what has been pushed; NULL = every message pushed so far.  laser: the header of the corrected scans
+ * (the angle cache is the first scan's, :129-137, so one geometry).  n_readings must equal the handle's first scan's, which
+ * fixes scan_count_.
+ * out_xyz[n_msgs][n_readings][3], out_valid[n_msgs][n_readings]: row k is the cloud of the scan callback k corrected, that
+ * is message k - 1, row 0 the scan the previous call left queued; rows of queued or refused callbacks are zeros with
+ * valid 0.  records[n_msgs] (may be NULL).
+ * Per call: k_msync_walk (one wave, the callbacks in order), k_msync_windows (one wave per callback: PruneImuDeque's
+ * integration, bit for bit imu_time_ / imu_rot_*, and PruneOdomDeque's increment), lslam_deskew's own k_deskew_batch on
+ * the records they wrote, and k_msync_blank.  The host form waits once, at its end.  The _dev form takes ranges, out_xyz,
+ * out_valid and records in HBM, is asynchronous on lslam_stream() and makes no host wait (stamps, time_increments and the
+ * *_seen arrays stay host arrays and have been copied when it returns).
+ * Refused with LSLAM_ERR_INVALID_ARGUMENT, nothing enqueued and no state changed: what lslam_deskew_batch refuses, a deskew
+ * handle of another context, another n_readings than the first scan's, *_seen that decrease or exceed the pushed count.
+ * LSLAM_ERR_UNSUPPORTED: more than 65535 callbacks per call. */
+int lslam_msync_scans(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_laser* laser, int n_msgs, int n_readings,
+                      const float* ranges, int ranges_stride, const double* stamps, const float* time_increments,
+                      const int64_t* imu_seen, const int64_t* odom_seen, float* out_xyz, uint8_t* out_valid,
+                      lslam_msync_record* records);
+int lslam_msync_scans_dev(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_laser* laser, int n_msgs, int n_readings,
+                          const float* ranges_dev, int ranges_stride, const double* stamps, const float* time_increments,
+                          const int64_t* imu_seen, const int64_t* odom_seen, float* out_xyz_dev, uint8_t* out_valid_dev,
+                          lslam_msync_record* records_dev);
+/* Debug read-back of the LAST call's integrated samples (imu_time_ / imu_rot_* of :207-243), for the parity tests: callback k
+ * owns [imu_first[k], imu_first[k + 1]) of imu_time[] and imu_rot_xyz[][3]; imu_first has n_msgs + 1 entries.  With
+ * capacity 0 only imu_first is filled (to size the arrays); a capacity below imu_first[n_msgs] is refused.  Waits. */
+int lslam_msync_read_windows(lslam_msync* h, int32_t* imu_first, double* imu_time, double* imu_rot_xyz, int capacity);
+/* out = {scan callbacks, scans corrected, scans refused, launches of the three msync kernels, buffer growths (device or
+ * pinned), host waits}.  The two scan counts come from the device and wait for the calls enqueued so far. */
+int lslam_msync_stats(lslam_msync* h, int64_t out[6]);
+
+/* ---------------------------------------------------------------------------------------- */
 /* lesson4 GMapping hit/visit count map (lesson4_gmapping_node: GMapping::ComputeMap /        */
 /* PublishMap, lesson4/src/gmapping/gmapping.cc:127-242, over ScanMatcherMap = G/map.h +      */
 /* G/harray2d.h, traced by GridLineTraversal::gridLine, G/gridlinetraversal.h; short name     */
