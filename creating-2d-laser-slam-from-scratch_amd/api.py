@@ -999,6 +999,10 @@ def lib() -> C.CDLL:
     L.lslam_map_set_cloud.argtypes = [vp, vp, vp, i32, C.POINTER(HectorScan), C.POINTER(i32)]
     L.lslam_hector_process_many_deskewed.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                      vp, vp]
+    L.lslam_hector_process_many_clouds.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_process_many_clouds_dev.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.lslam_hector_process_many_synced.argtypes = [vp, vp, C.POINTER(HectorScan), C.POINTER(MsyncLaser), i32, i32, vp, i32, vp, vp,
+                                                   vp, vp, vp, vp, vp, vp]
     L.lslam_clock_sample.argtypes = [vp, vp]
     L.lslam_matcher_get_option.argtypes = [vp, i32]
     L.lslam_matcher_set_option.argtypes = [vp, i32, i32]
@@ -2252,6 +2256,55 @@ class HectorProcessor:
             ir[0].ctypes.data, ir[1].ctypes.data, ir[2].ctypes.data, None if hints is None else hints.ctypes.data,
             None if flags is None else flags.ctypes.data, out.ctypes.data))
         return out
+
+    def process_many_clouds(self, xyz, scan: HectorScan, valid=None, take=None, pose_hints=None, map_without_matching=None) -> np.ndarray:
+        """xyz: [n_scans, n_points, 3] float32 clouds in the de-skew's layout (Deskewer.batch, MotionSync.scans), valid
+        [n_scans, n_points] or None = every point, take [n_scans] or None = every scan -> HECTOR_RECORD[n_scans].  A scan with
+        take == 0 changes nothing of the processor; its record is zero with n_points = -1."""
+        x = np.ascontiguousarray(xyz, dtype=np.float32)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError("xyz must be [n_scans, n_points, 3]")
+        n, npts = x.shape[0], x.shape[1]
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid).astype(bool).astype(np.uint8)).reshape(n, npts)
+        t = None if take is None else np.ascontiguousarray(np.asarray(take).astype(bool).astype(np.uint8)).reshape(n)
+        hints, flags = self._hints_flags(n, pose_hints, map_without_matching)
+        out = np.zeros(n, HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many_clouds(
+            self.h, C.byref(scan), n, npts, x.ctypes.data, None if v is None else v.ctypes.data,
+            None if t is None else t.ctypes.data, None if hints is None else hints.ctypes.data,
+            None if flags is None else flags.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_clouds_dev(self, n_scans: int, n_points: int, xyz_ptr: int, valid_ptr, take_ptr, take_stride: int,
+                                scan: HectorScan, pose_hints=None, map_without_matching=None) -> np.ndarray:
+        """The same on clouds in HBM (xyz float32, valid uint8 or None).  take_ptr: int32 words in HBM, scan k is taken iff
+        word k * take_stride is > 0 (None: every scan) -- the `status` field of an MSYNC_RECORD array with take_stride =
+        MSYNC_RECORD.itemsize // 4 serves as it stands."""
+        hints, flags = self._hints_flags(n_scans, pose_hints, map_without_matching)
+        out = np.zeros(n_scans, HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many_clouds_dev(
+            self.h, C.byref(scan), n_scans, n_points, xyz_ptr, valid_ptr, take_ptr, int(take_stride),
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_synced(self, sync: "MotionSync", laser, ranges, scan: HectorScan, stamps, time_increments, imu_seen=None,
+                       odom_seen=None, pose_hints=None, map_without_matching=None, n_readings=None):
+        """n ScanCallbacks of lesson5's node (what MotionSync.scans takes; the IMU and odometry messages pushed into `sync`
+        before) chained into update(): -> (HECTOR_RECORD[n], MSYNC_RECORD[n]), record k of both for callback k.  A callback
+        whose status is not MSYNC_CORRECTED changes nothing of the processor.  One host synchronisation."""
+        hdr, t, ti, seen = MotionSync._small(laser, stamps, time_increments, imu_seen, odom_seen)
+        n = len(t)
+        r = np.ascontiguousarray(ranges, dtype=np.float32).reshape(n, -1) if n else np.zeros((0, 0), np.float32)
+        stride = r.shape[1]
+        nr = stride if n_readings is None else int(n_readings)
+        hints, flags = self._hints_flags(n, pose_hints, map_without_matching)
+        out, rec = np.zeros(n, HECTOR_RECORD), np.zeros(n, MSYNC_RECORD)
+        self.ctx.check(self.L.lslam_hector_process_many_synced(
+            self.h, sync.h, C.byref(scan), C.byref(hdr), n, nr, r.ctypes.data, stride, t.ctypes.data, ti.ctypes.data,
+            None if seen[0] is None else seen[0].ctypes.data, None if seen[1] is None else seen[1].ctypes.data,
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data, out.ctypes.data,
+            rec.ctypes.data))
+        return out, rec
 
     def process_many_points(self, containers, pose_hints=None, map_without_matching=None, origos_xy=None, counts=None) -> np.ndarray:
         """containers: a list of (n, 2) float32 arrays in level-0 cell units, or -- with `counts` -- one packed array."""

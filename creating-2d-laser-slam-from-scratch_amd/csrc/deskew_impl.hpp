@@ -70,4 +70,13 @@ int deskew_launch_records(lslam_deskew* d, int n_scans, int n_readings, const fl
                           uint8_t* d_valid);
 lslam_context* deskew_context(lslam_deskew* d);
 
+// csrc/motion_sync.hip for the streamed Hector processor (lslam_hector_process_many_synced), which must refuse a call before
+// it enqueues anything: the handle's context, and exactly the checks of lslam_msync_scans_dev on the host arguments (the
+// device pointers are the caller's own buffers).  Touches no state and no device.
+lslam_context* msync_context(const lslam_msync* h);
+int msync_check_scans(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_laser* laser, int n_msgs, int n_readings,
+                      const double* stamps, const float* time_increments, const int64_t* imu_seen, const int64_t* odom_seen);
+// the caller has waited for the context's stream: the pinned staging area is free again and the state copy has landed
+void msync_stream_drained(lslam_msync* h);
+
 }  // namespace lslam

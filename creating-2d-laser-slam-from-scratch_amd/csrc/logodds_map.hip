@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "deskew_impl.hpp"  // msync_context, msync_check_scans, msync_stream_drained
 
 using namespace lslam;
 
@@ -1704,6 +1705,69 @@ k_hs_apply(HsLevels lv, const HsState* __restrict__ st, const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// GATED streamed chain (lslam_hector_process_many_clouds[_dev], lslam_hector_process_many_synced): whether a scan is taken is
+// decided on the device -- lslam_msync_record::status, written by k_msync_walk earlier in the same stream -- so the chain
+// k_hg_cloud_container -> k_hg_match_* -> k_hs_mark -> k_hs_apply reads a TAKE word from HBM first: the scan is taken iff
+// *take > 0 (LSLAM_MSYNC_CORRECTED is 1, QUEUED 0, every refusal negative); take == nullptr takes every scan.  The host
+// hands each launch the address of its scan's word (take + k * stride), so a status field inside an array of records serves
+// as it stands.  The arithmetic is hector_compact / hector_cloud_point and hs_scan_*: a taken scan's bits are those of the
+// ungated chain.  A scan that is not taken:
+//   k_hg_cloud_container   returns before its first store: the live container and its count stay the last taken scan's
+//   k_hg_match_*           returns before hs_begin's barrier (the word is uniform over the block); one thread writes the
+//                          record of a scan that was not taken (all zero, n_points = -1) and st->updated = 0 -- WITHOUT
+//                          that store the state block still holds the previous scan's decision, and
+//   k_hs_mark / k_hs_apply (unchanged) would apply the previous scan's update a second time; with it they return at once
+// So a refused scan costs four launches of blocks that load one word and leave, and changes nothing of the processor: it is
+// NOT a scan with an empty container, which would reset n_live / n_cached and the cached origo (hs_finish).
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool hg_taken(const int32_t* take) { return !take || *take > 0; }
+
+// ONE thread: what a scan that was not taken leaves behind
+__device__ __forceinline__ void hg_skip(HsState* st, lslam_hector_record* __restrict__ rec) {
+  st->updated = 0;
+  if (rec) {
+    for (int q = 0; q < 3; q++) rec->pose[q] = 0.0f;
+    for (int q = 0; q < 9; q++) rec->cov[q] = 0.0f;
+    rec->updated = 0;
+    rec->n_points = -1;
+    rec->pad[0] = rec->pad[1] = 0;
+  }
+}
+
+// k_hector_cloud_container behind the take word; valid == nullptr: every point is valid
+__global__ void __launch_bounds__(1024)
+k_hg_cloud_container(ProjectCfg c, const int32_t* __restrict__ take, const float* __restrict__ xyz,
+                     const uint8_t* __restrict__ valid, float* __restrict__ out_xy, int* __restrict__ out_n) {
+  if (!hg_taken(take)) return;
+  hector_compact(c.n, out_xy, out_n, [&](int i, float& ox, float& oy) {
+    if (valid && !valid[i]) return false;
+    return hector_cloud_point(c, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ox, oy);
+  });
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_hg_match_reg(GnLevels lv, HsScan sc, const int32_t* __restrict__ take, const float* __restrict__ pts, const int* n_src,
+               float* __restrict__ cache_dst, HsState* st, lslam_hector_record* __restrict__ rec) {
+  if (!hg_taken(take)) {
+    if (threadIdx.x == 0) hg_skip(st, rec);
+    return;
+  }
+  hs_scan_reg<NT, PMAX>(lv, sc, pts, n_src, cache_dst, st, rec);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_hg_match_fast(GnLevels lv, HsScan sc, const int32_t* __restrict__ take, const float* __restrict__ pts, const int* n_src,
+                float* __restrict__ cache_dst, int pts_in_lds, HsState* st, lslam_hector_record* __restrict__ rec) {
+  if (!hg_taken(take)) {
+    if (threadIdx.x == 0) hg_skip(st, rec);
+    return;
+  }
+  hs_scan_fast<NT>(lv, sc, pts, n_src, cache_dst, pts_in_lds, st, rec);
+}
+
+// ------------------------------------------------------------------------------------------
 // HECTOR FLEET (lslam_hector_fleet_*): R streamed processors, each on its own map, advance one scan each per STEP, and a step
 // is the chain of ONE processor -- [k_hf_project] -> k_hf_match_* -> k_hf_mark -> k_hf_apply -- whatever R is.  The members
 // are independent SLAM sessions, so nothing orders one against another inside a launch; within a member, stream order is
@@ -3368,6 +3432,11 @@ struct lslam_hector {
   lslam_deskew* deskew = nullptr;
   DevBuf<float> d_xyz;
   DevBuf<uint8_t> d_valid;
+  // gated forms: the host form's take words, and the synced form's lslam_msync_records with their pinned way down
+  DevBuf<int32_t> d_take;
+  DevBuf<lslam_msync_record> d_msrec;
+  lslam_msync_record* h_msrec = nullptr;
+  size_t h_msrec_cap = 0;
   int64_t n_scans = 0, n_updates = 0, n_calls = 0, n_syncs = 0;
 };
 
@@ -3412,6 +3481,13 @@ struct HsCall {
   const lslam_hector_scan* scan = nullptr;   // ranges form: project scan k's readings into the map's resident container
   int n_readings = 0;
   bool cloud = false;                        // de-skewed form: scan k's cloud (h->d_xyz, h->d_valid) goes there instead
+  bool gated = false;                        // cloud forms: scan k's cloud (d_xyz, d_valid; d_valid null: all valid) goes there
+  const float* d_xyz = nullptr;              //   through the gated chain, which takes it iff d_take[k * take_stride] > 0
+  const uint8_t* d_valid = nullptr;          //   (d_take null: every scan)
+  const int32_t* d_take = nullptr;
+  int take_stride = 0;
+  lslam_msync* sync = nullptr;               // synced form: the handle whose walk wrote the take words, and where its
+  lslam_msync_record* sync_out = nullptr;    //   records (h->d_msrec) go when they come down with the processor's
   const float* d_points = nullptr;           // container form: the packed points in HBM,
   const int32_t* n_points = nullptr;         //   their host counts (offsets) and
   const float* origos = nullptr;             //   origos (may be null)
@@ -3518,8 +3594,13 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     }
     const float* pts;
     const int* n_src;
+    const int32_t* take = c.d_take ? c.d_take + (size_t)k * (size_t)c.take_stride : nullptr;
     if (c.scan) {
-      if (c.cloud)
+      if (c.gated)
+        launch(ctx, "hg_cloud_container", k_hg_cloud_container, dim3(1), dim3(1024), 0, pc, take,
+               c.d_xyz + (size_t)3 * k * c.n_readings, c.d_valid ? c.d_valid + (size_t)k * c.n_readings : (const uint8_t*)nullptr,
+               map->d_scan.p, d_n_live);
+      else if (c.cloud)
         launch(ctx, "hs_cloud_container", k_hector_cloud_container, dim3(1), dim3(1024), 0, pc,
                (const float*)(h->d_xyz.p + (size_t)3 * k * c.n_readings), (const uint8_t*)(h->d_valid.p + (size_t)k * c.n_readings),
                map->d_scan.p, d_n_live);
@@ -3541,9 +3622,21 @@ int hs_run(lslam_hector* h, const HsCall& c) {
 #define LSLAM_HS_FAST(NT)                                                                                                    \
   launch(ctx, "hs_match", k_hs_match_fast<NT>, dim3(1), dim3(NT), form.lds, lv, sc, pts, n_src, map->d_cached.p, form.in_lds, \
          h->d_state, rec)
-    LSLAM_GN_DISPATCH(form, LSLAM_HS_REG, LSLAM_HS_FAST);
+#define LSLAM_HG_REG(NT, PMAX)                                                                                                 \
+  launch(ctx, "hg_match", k_hg_match_reg<NT, PMAX>, dim3(1), dim3(NT), form.lds, lv, sc, take, pts, n_src, map->d_cached.p, \
+         h->d_state, rec)
+#define LSLAM_HG_FAST(NT)                                                                                                      \
+  launch(ctx, "hg_match", k_hg_match_fast<NT>, dim3(1), dim3(NT), form.lds, lv, sc, take, pts, n_src, map->d_cached.p, form.in_lds, \
+         h->d_state, rec)
+    if (c.gated) {
+      LSLAM_GN_DISPATCH(form, LSLAM_HG_REG, LSLAM_HG_FAST);
+    } else {
+      LSLAM_GN_DISPATCH(form, LSLAM_HS_REG, LSLAM_HS_FAST);
+    }
 #undef LSLAM_HS_REG
 #undef LSLAM_HS_FAST
+#undef LSLAM_HG_REG
+#undef LSLAM_HG_FAST
     launch(ctx, "hs_mark", k_hs_mark, ugrid, ublock, 0, ul, (const HsState*)h->d_state, pts, (const float*)map->d_cached.p);
     launch(ctx, "hs_apply", k_hs_apply, ugrid, ublock, 0, ul, (const HsState*)h->d_state, pts, (const float*)map->d_cached.p);
   }
@@ -3551,13 +3644,21 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   // ---- end of the call: the records and the state down, ONE wait
   LSLAM_HIP(ctx, hipMemcpyAsync(h->h_rec, h->d_rec.p, (size_t)c.n_scans * sizeof(lslam_hector_record), hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipMemcpyAsync(h->h_io + kHsPersistWords, h->d_state, kHsPersistWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (c.sync_out)
+    LSLAM_HIP(ctx, hipMemcpyAsync(h->h_msrec, h->d_msrec.p, (size_t)c.n_scans * sizeof(lslam_msync_record), hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   h->n_syncs++;
   h->n_calls++;
-  h->n_scans += c.n_scans;
   memcpy(&h->mirror, h->h_io + kHsPersistWords, kHsPersistWords * 4);
-  for (int k = 0; k < c.n_scans; k++) h->n_updates += h->h_rec[k].updated != 0;
+  int n_taken = 0;  // (the gated chain marks the record of a scan it did not take with n_points = -1)
+  for (int k = 0; k < c.n_scans; k++) {
+    n_taken += h->h_rec[k].n_points >= 0;
+    h->n_updates += h->h_rec[k].updated != 0;
+  }
+  h->n_scans += n_taken;
   if (c.out) memcpy(c.out, h->h_rec, (size_t)c.n_scans * sizeof(lslam_hector_record));
+  if (c.sync_out) memcpy(c.sync_out, h->h_msrec, (size_t)c.n_scans * sizeof(lslam_msync_record));
+  if (c.sync) msync_stream_drained(c.sync);
   // what the host side of the map must know so that every lslam_map_* call goes on working on it
   if (n_levels > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
     map->n_cached = h->mirror.n_cached;
@@ -3565,7 +3666,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     map->cached_origo[1] = h->mirror.cached_origo[1];
   }
   map->gn_host_n = -1;  // d_cached was rewritten on the device
-  if (c.scan) {         // the resident container of lslam_map_set_scan is the last scan's
+  if (c.scan && n_taken > 0) {  // the resident container of lslam_map_set_scan is the last (taken) scan's
     map->n_scan = h->mirror.n_live;
     map->scan_origo[0] = scan_origo[0];
     map->scan_origo[1] = scan_origo[1];
@@ -3605,6 +3706,9 @@ void lslam_hector_destroy(lslam_hector* h) {
   if (h->h_io) (void)hipHostFree(h->h_io);
   if (h->h_rec) (void)hipHostFree(h->h_rec);
   if (h->h_ranges) (void)hipHostFree(h->h_ranges);
+  if (h->h_msrec) (void)hipHostFree(h->h_msrec);
+  h->d_take.release();
+  h->d_msrec.release();
   h->d_rec.release();
   h->d_ranges.release();
   h->d_counts.release();
@@ -3714,6 +3818,135 @@ int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan*
   c.hints = pose_hints;
   c.no_match = map_without_matching;
   c.out = out;
+  return hs_run(h, c);
+}
+
+int lslam_hector_process_many_clouds_dev(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_points,
+                                         const float* xyz_dev, const uint8_t* valid_dev, const int32_t* take_dev,
+                                         int take_stride, const float* pose_hints, const uint8_t* map_without_matching,
+                                         lslam_hector_record* out) {
+  if (!h || n_scans < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_scans == 0) return LSLAM_OK;
+  if (!scan || (n_points > 0 && !xyz_dev) || (take_dev && take_stride < 1)) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  int rc = hs_check(h, "lslam_hector_process_many_clouds", n_points);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_points, 1) + 4));
+  HsCall c;
+  c.n_scans = n_scans;
+  c.capacity = n_points;
+  c.scan = scan;
+  c.n_readings = n_points;
+  c.gated = true;
+  c.d_xyz = xyz_dev;
+  c.d_valid = valid_dev;
+  c.d_take = take_dev;
+  c.take_stride = take_stride;
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.out = out;
+  return hs_run(h, c);
+}
+
+int lslam_hector_process_many_clouds(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_points,
+                                     const float* xyz, const uint8_t* valid, const uint8_t* take, const float* pose_hints,
+                                     const uint8_t* map_without_matching, lslam_hector_record* out) {
+  if (!h || n_scans < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_scans == 0) return LSLAM_OK;
+  if (!scan || (n_points > 0 && !xyz)) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = h->map->ctx;
+  int rc = hs_check(h, "lslam_hector_process_many_clouds", n_points);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // pinned: [xyz | take words | valid bytes] (the call ends with a wait: the buffer is never in flight here)
+  const size_t total = (size_t)n_scans * (size_t)n_points;
+  const size_t o_take = 3 * total, o_valid = o_take + (size_t)n_scans, words = o_valid + (total + 3) / 4;
+  LSLAM_HIP(ctx, h->d_xyz.reserve(std::max(3 * total, (size_t)1)));
+  if (valid) LSLAM_HIP(ctx, h->d_valid.reserve(std::max(total, (size_t)1)));
+  if (take) LSLAM_HIP(ctx, h->d_take.reserve((size_t)n_scans));
+  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, words);
+  if (rc) return rc;
+  if (total > 0) {
+    memcpy(h->h_ranges, xyz, 3 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_xyz.p, h->h_ranges, 3 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (valid) {
+      memcpy(h->h_ranges + o_valid, valid, total);
+      LSLAM_HIP(ctx, hipMemcpyAsync(h->d_valid.p, h->h_ranges + o_valid, total, hipMemcpyHostToDevice, ctx->stream));
+    }
+  }
+  if (take) {
+    int32_t* t = reinterpret_cast<int32_t*>(h->h_ranges + o_take);
+    for (int k = 0; k < n_scans; k++) t[k] = take[k] ? 1 : 0;
+    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_take.p, t, (size_t)n_scans * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return lslam_hector_process_many_clouds_dev(h, scan, n_scans, n_points, h->d_xyz.p, valid ? h->d_valid.p : (const uint8_t*)nullptr,
+                                              take ? h->d_take.p : (const int32_t*)nullptr, 1, pose_hints, map_without_matching, out);
+}
+
+int lslam_hector_process_many_synced(lslam_hector* h, lslam_msync* sync, const lslam_hector_scan* scan,
+                                     const lslam_msync_laser* laser, int n_msgs, int n_readings, const float* ranges,
+                                     int ranges_stride, const double* stamps, const float* time_increments,
+                                     const int64_t* imu_seen, const int64_t* odom_seen, const float* pose_hints,
+                                     const uint8_t* map_without_matching, lslam_hector_record* out,
+                                     lslam_msync_record* sync_records) {
+  if (!h || !sync || n_msgs < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_msgs == 0) return LSLAM_OK;
+  if (!scan || !ranges) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_map* map = h->map;
+  lslam_context* ctx = map->ctx;
+  // ---- everything that can refuse the call, before anything is enqueued or either handle changes
+  if (msync_context(sync) != ctx)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_synced: the lslam_msync handle belongs to another context than the map");
+  int rc = hs_check(h, "lslam_hector_process_many_synced", n_readings);
+  if (rc) return rc;
+  if (ranges_stride < n_readings)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_synced: ranges_stride >= n_readings is required");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  if (!h->deskew) {
+    rc = lslam_deskew_create(ctx, &h->deskew);
+    if (rc) return rc;
+  }
+  rc = msync_check_scans(sync, h->deskew, laser, n_msgs, n_readings, stamps, time_increments, imu_seen, odom_seen);
+  if (rc) return rc;
+  // ---- buffers: ranges up through pinned staging; clouds and the walk's records stay in HBM
+  const size_t total = (size_t)n_msgs * (size_t)n_readings;
+  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * n_readings + 4));
+  LSLAM_HIP(ctx, h->d_ranges.reserve(total));
+  LSLAM_HIP(ctx, h->d_xyz.reserve(3 * total));
+  LSLAM_HIP(ctx, h->d_valid.reserve(total));
+  LSLAM_HIP(ctx, h->d_msrec.reserve((size_t)n_msgs));
+  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, total);
+  if (rc) return rc;
+  if (sync_records) {
+    rc = hs_pinned_reserve(ctx, &h->h_msrec, &h->h_msrec_cap, (size_t)n_msgs);
+    if (rc) return rc;
+  }
+  for (int k = 0; k < n_msgs; k++)
+    memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
+  LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  // the node's callbacks for the whole call: walk, windows, ONE de-skew launch, blank -- asynchronous, no wait
+  rc = lslam_msync_scans_dev(sync, h->deskew, laser, n_msgs, n_readings, h->d_ranges.p, n_readings, stamps, time_increments, imu_seen,
+                             odom_seen, h->d_xyz.p, h->d_valid.p, h->d_msrec.p);
+  if (rc) return rc;
+  static_assert(offsetof(lslam_msync_record, status) == 0 && sizeof(lslam_msync_record) % sizeof(int32_t) == 0,
+                "lslam_msync_record::status is the take word of its callback");
+  HsCall c;
+  c.n_scans = n_msgs;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.gated = true;
+  c.d_xyz = h->d_xyz.p;
+  c.d_valid = h->d_valid.p;
+  c.d_take = &h->d_msrec.p->status;
+  c.take_stride = (int)(sizeof(lslam_msync_record) / sizeof(int32_t));
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.out = out;
+  c.sync = sync;
+  c.sync_out = sync_records;
   return hs_run(h, c);
 }
 

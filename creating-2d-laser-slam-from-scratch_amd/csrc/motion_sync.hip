@@ -542,6 +542,19 @@ int ms_reset_state(lslam_msync* h) {
 
 }  // namespace
 
+lslam_context* lslam::msync_context(const lslam_msync* h) { return h->ctx; }
+
+int lslam::msync_check_scans(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_laser* laser, int n_msgs, int n_readings,
+                             const double* stamps, const float* time_increments, const int64_t* imu_seen, const int64_t* odom_seen) {
+  const void* const callers = h;  // stands for the device pointers, which ms_check only compares with NULL
+  return ms_check(h, deskew, laser, n_msgs, n_readings, callers, n_readings, stamps, time_increments, imu_seen, odom_seen, callers, callers);
+}
+
+void lslam::msync_stream_drained(lslam_msync* h) {
+  h->stage_used = 0;
+  ms_poll_state(h);
+}
+
 extern "C" {
 
 int lslam_msync_create(lslam_context* ctx, int use_imu, int use_odom, lslam_msync** out) {

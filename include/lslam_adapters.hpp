@@ -451,6 +451,7 @@ class MapRepGpu {
 // MapRepGpu like the reference's processor owns its MapRepMultiMap (:61).  Use it where a stretch of scans is at hand
 // (a recorded log, a queue that has run full); HectorMapRepGpu (integration/hector_map_rep_gpu.hpp) is for the reference's
 // own processor driving the device one call at a time.
+class LidarUndistortionGpu;
 class HectorSlamProcessorGpu {
  public:
   // HectorSlamProcessor(mapResolution, mapSizeX, mapSizeY, startCoords, multi_res_size) (:57-68) + the device context
@@ -501,6 +502,33 @@ class HectorSlamProcessorGpu {
                                              imuRotX, imuRotY, imuRotZ, poseHints,
                                              mapWithoutMatching ? flags_.data() : nullptr, records));
   }
+  // update() for nScans clouds that are de-skewed already (LidarUndistortionGpu::CorrectLaserScans' / ScanCallbacks' layout:
+  // xyz nScans x nPoints x 3, valid nScans x nPoints or nullptr = every point).  take[nScans] (nullptr = all): a scan with
+  // take false never reaches update() -- nothing of the processor changes, its record is zero with n_points = -1
+  void updateManyClouds(const lslam_hector_scan& scan, int nScans, int nPoints, const float* xyz, const uint8_t* valid,
+                        const bool* take, const float* poseHints, const bool* mapWithoutMatching, lslam_hector_record* records) {
+    setFlags(nScans, mapWithoutMatching);
+    take_.assign((size_t)(nScans > 0 ? nScans : 0), 0);
+    for (int k = 0; k < nScans && take; ++k) take_[(size_t)k] = take[k] ? 1 : 0;
+    check(lslam_hector_process_many_clouds(h_, &scan, nScans, nPoints, xyz, valid, take ? take_.data() : nullptr, poseHints,
+                                           mapWithoutMatching ? flags_.data() : nullptr, records));
+  }
+  // the same on clouds in HBM (CorrectLaserScansDev's output); scan k is taken iff takeDev[k * takeStride] > 0 (nullptr = all):
+  // &recordsDev[0].status of lslam_msync_record with takeStride = sizeof(lslam_msync_record) / 4 serves as it stands
+  void updateManyCloudsDev(const lslam_hector_scan& scan, int nScans, int nPoints, const float* xyzDev, const uint8_t* validDev,
+                           const int32_t* takeDev, int takeStride, const float* poseHints, const bool* mapWithoutMatching,
+                           lslam_hector_record* records) {
+    setFlags(nScans, mapWithoutMatching);
+    check(lslam_hector_process_many_clouds_dev(h_, &scan, nScans, nPoints, xyzDev, validDev, takeDev, takeStride, poseHints,
+                                               mapWithoutMatching ? flags_.data() : nullptr, records));
+  }
+  // lesson5's node in front of update(): nMsgs ScanCallbacks of `node` (its ImuCallback(s) / OdomCallback(s) before), the
+  // scan each one corrects straight into update() on the device; a scan the node refuses never reaches it.  records[k] and
+  // syncRecords[k] (either may be nullptr) belong to callback k.  One host synchronisation.  (Defined below the node.)
+  inline void updateManySynced(LidarUndistortionGpu& node, const lslam_hector_scan& scan, const lslam_msync_laser& laser, int nMsgs,
+                               int nReadings, const float* ranges, int rangesStride, const double* stamps,
+                               const float* timeIncrements, const int64_t* imuSeen, const int64_t* odomSeen, const float* poseHints,
+                               const bool* mapWithoutMatching, lslam_hector_record* records, lslam_msync_record* syncRecords);
   void reset() { check(lslam_hector_reset(h_)); }  // :111-117
   // getLastScanMatchPose / getLastScanMatchCovariance (:120-122)
   void getLastScanMatchPose(float out[3]) { check(lslam_hector_state(h_, out, nullptr, nullptr)); }
@@ -519,12 +547,16 @@ class HectorSlamProcessorGpu {
   void check(int rc) {
     if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
   }
+  void setFlags(int nScans, const bool* mapWithoutMatching) {
+    flags_.assign((size_t)(nScans > 0 ? nScans : 0), 0);
+    for (int k = 0; k < nScans && mapWithoutMatching; ++k) flags_[(size_t)k] = mapWithoutMatching[k] ? 1 : 0;
+  }
   lslam_context* ctx_;
   MapRepGpu map_;
   lslam_hector* h_ = nullptr;
   float minDist_ = 0.4f, minAngle_ = 0.13f;
   std::vector<float> pts_;
-  std::vector<uint8_t> flags_;
+  std::vector<uint8_t> flags_, take_;
 };
 
 // R HectorSlamProcessorGpu advanced together (lslam_hector_fleet_*): one robot's scan k+1 needs its scan k, but robots need
@@ -707,6 +739,7 @@ class LidarUndistortionGpu {
   void Reset() { check(lslam_msync_reset(sync())); }
   // {scan callbacks, scans corrected, scans refused, launches of the synchronisation's kernels, buffer growths, host waits}
   void syncStats(int64_t out[6]) { check(lslam_msync_stats(sync(), out)); }
+  lslam_msync* syncHandle() { return sync(); }  // for HectorSlamProcessorGpu::updateManySynced
 
  private:
   void check(int rc) {
@@ -721,6 +754,18 @@ class LidarUndistortionGpu {
   lslam_deskew* h_ = nullptr;
   lslam_msync* sync_ = nullptr;
 };
+
+inline void HectorSlamProcessorGpu::updateManySynced(LidarUndistortionGpu& node, const lslam_hector_scan& scan,
+                                                     const lslam_msync_laser& laser, int nMsgs, int nReadings, const float* ranges,
+                                                     int rangesStride, const double* stamps, const float* timeIncrements,
+                                                     const int64_t* imuSeen, const int64_t* odomSeen, const float* poseHints,
+                                                     const bool* mapWithoutMatching, lslam_hector_record* records,
+                                                     lslam_msync_record* syncRecords) {
+  setFlags(nMsgs, mapWithoutMatching);
+  check(lslam_hector_process_many_synced(h_, node.syncHandle(), &scan, &laser, nMsgs, nReadings, ranges, rangesStride, stamps,
+                                         timeIncrements, imuSeen, odomSeen, poseHints,
+                                         mapWithoutMatching ? flags_.data() : nullptr, records, syncRecords));
+}
 
 // lesson1's LaserScan (lesson1/src/feature_detection.cc): ScanCallback's corner extraction, for one scan or many per
 // launch.  cornerRanges is what the node publishes as corner_scan.ranges (its first n entries): the range of every

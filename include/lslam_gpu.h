@@ -887,6 +887,52 @@ int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan*
                                        const int32_t* imu_first, const double* imu_time, const double* imu_rot_x,
                                        const double* imu_rot_y, const double* imu_rot_z, const float* pose_hints,
                                        const uint8_t* map_without_matching, lslam_hector_record* out);
+/* GATED forms: clouds that are de-skewed already, and lesson5's whole node in front of update().  Whether a scan reaches
+ * HectorSlamProcessor::update (HectorSlamProcessor.h:81-108) is decided by a per-scan TAKE word the kernels read from HBM:
+ * the reference's node publishes nothing for a scan PruneImuDeque / PruneOdomDeque refuse (lidar_undistortion.cc:96-125), so
+ * rosPointCloudToDataContainer (hector_slam.cc:320-362) and update() never run for it.  A scan that is NOT TAKEN changes
+ * nothing of the processor: the three state vectors, the covariance, the live (resident) and the cached container with their
+ * counts and origo and every plane stay as they were; its record is all zero except n_points = -1 (the fleet's convention
+ * for active[i] == 0).  It is NOT an empty container, which update() would process (and which would empty the cached
+ * container the next update of levels > 0 reads).  `scans` of lslam_hector_stats advances by the taken scans only; the map's
+ * resident container is the last TAKEN scan's and is untouched when none was taken.  pose_hints NULL chains from
+ * lastScanMatchPose, and a scan that is not taken does not break the chain; hints and flags of such a scan are not read.
+ * A scan is the chain container, match, mark, apply -- 4 launches, taken or not: a scan that is not taken costs four launches
+ * of blocks that load one word and return.  All three make ONE host synchronisation, at the end of the call, whatever the
+ * count; inputs go up through pinned staging.  What lslam_hector_process_many refuses is refused here, before anything is
+ * enqueued; NULL handles are LSLAM_ERR_INVALID_ARGUMENT without a device.
+ *
+ * update() for n_scans clouds of n_points beams in the de-skew's layout: xyz[n_scans][n_points][3] float32,
+ * valid[n_scans][n_points] (NULL: every point valid), through rosPointCloudToDataContainer on the device.
+ * take[n_scans] (NULL: all): a scan with take == 0 is not taken (see above). */
+int lslam_hector_process_many_clouds(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_points,
+                                     const float* xyz, const uint8_t* valid, const uint8_t* take,
+                                     const float* pose_hints, const uint8_t* map_without_matching, lslam_hector_record* out);
+/* the same on clouds already in HBM (Deskewer.batch_dev, MotionSync.scans_dev, IcpMatcher.convert_dev): nothing but
+ * hints and flags goes up; taken iff take_dev[k * take_stride] > 0 (NULL: all).  take_stride counts int32 words:
+ * &records_dev[0].status of lslam_msync_record with sizeof(lslam_msync_record) / 4 (22) serves as it stands --
+ * LSLAM_MSYNC_CORRECTED is 1, QUEUED 0, every refusal negative. */
+int lslam_hector_process_many_clouds_dev(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_points,
+                                         const float* xyz_dev, const uint8_t* valid_dev, const int32_t* take_dev,
+                                         int take_stride, const float* pose_hints, const uint8_t* map_without_matching,
+                                         lslam_hector_record* out);
+/* n_msgs ScanCallbacks of lesson5's node chained into update(): lslam_msync_scans_dev on buffers the processor owns
+ * (its lazily created lslam_deskew, as _deskewed uses), then the gated chain per callback on the status the walk wrote.
+ * Record k of both outputs belongs to callback k, which corrects message k - 1 (CacheLaserScan's one-scan lag,
+ * lidar_undistortion.cc:142-156; row 0: the scan the previous call left queued).  sync_records may be NULL.  The arguments
+ * from `laser` to `odom_seen` are lslam_msync_scans'.  Refused, with neither handle changed: what lslam_msync_scans_dev
+ * refuses (LSLAM_ERR_INVALID_ARGUMENT: another n_readings than the handle's first scan's, *_seen that decrease or exceed the
+ * pushed count; LSLAM_ERR_UNSUPPORTED: more than 65535 callbacks) and a `sync` whose context is not the map's
+ * (LSLAM_ERR_INVALID_ARGUMENT). */
+struct lslam_msync;
+struct lslam_msync_laser;
+struct lslam_msync_record;
+int lslam_hector_process_many_synced(lslam_hector* h, struct lslam_msync* sync, const lslam_hector_scan* scan,
+                                     const struct lslam_msync_laser* laser, int n_msgs, int n_readings, const float* ranges,
+                                     int ranges_stride, const double* stamps, const float* time_increments,
+                                     const int64_t* imu_seen, const int64_t* odom_seen, const float* pose_hints,
+                                     const uint8_t* map_without_matching, lslam_hector_record* out,
+                                     struct lslam_msync_record* sync_records);
 /* getLastScanMatchPose / getLastScanMatchCovariance (:120-122) and lastMapUpdatePose; any pointer may be NULL.  Host only. */
 int lslam_hector_state(lslam_hector* h, float last_match_pose[3], float last_match_cov[9], float last_update_pose[3]);
 /* out = {scans processed, map updates made, calls that processed scans, waits for the stream those calls made}.  The last is
