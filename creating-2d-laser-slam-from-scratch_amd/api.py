@@ -931,6 +931,11 @@ def lib() -> C.CDLL:
     L.lslam_hector_fleet_process_many.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp, vp]
     L.lslam_hector_fleet_process_many_points.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.lslam_hector_fleet_stats.argtypes = [vp, vp]
+    L.lslam_hector_fleet_process_many_clouds.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_fleet_process_many_clouds_dev.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_hector_fleet_process_many_synced.argtypes = [vp, vp, C.POINTER(HectorScan), C.POINTER(MsyncLaser), i32, i32, vp, i32,
+                                                         vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_fleet_sync_stats.argtypes = [vp, vp]
     L.lslam_pool_create.argtypes = [i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_create_on.argtypes = [vp, i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_destroy.argtypes = [vp]
@@ -2427,6 +2432,81 @@ class HectorFleet:
             None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data,
             None if act is None else act.ctypes.data, out.ctypes.data))
         return out
+
+    def process_many_clouds(self, xyz, scan: HectorScan, valid=None, take=None, pose_hints=None, map_without_matching=None,
+                            active=None) -> np.ndarray:
+        """xyz: [n_steps, R, n_points, 3] float32 clouds in the de-skew's layout, valid [n_steps, R, n_points] or None = every
+        point, take [n_steps, R] or None = every scan -> HECTOR_RECORD[n_steps, R].  An entry is taken iff it is active and its
+        take flag is set; one that is not changes nothing of its member (record: zero with n_points = -1)."""
+        R = len(self.processors)
+        x = np.ascontiguousarray(xyz, dtype=np.float32)
+        if x.ndim != 4 or x.shape[1] != R or x.shape[3] != 3:
+            raise ValueError("xyz must be [n_steps, R, n_points, 3]")
+        n_steps, npts = x.shape[0], x.shape[2]
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid).astype(bool).astype(np.uint8)).reshape(n_steps, R, npts)
+        t = None if take is None else np.ascontiguousarray(np.asarray(take).astype(bool).astype(np.uint8)).reshape(n_steps, R)
+        hints, flags, act = self._per_scan(n_steps, pose_hints, map_without_matching, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_fleet_process_many_clouds(
+            self.h, C.byref(scan), n_steps, npts, x.ctypes.data, None if v is None else v.ctypes.data,
+            None if t is None else t.ctypes.data, None if hints is None else hints.ctypes.data,
+            None if flags is None else flags.ctypes.data, None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_clouds_dev(self, n_steps: int, n_points: int, xyz_ptrs, valid_ptrs, take_ptrs, take_stride: int,
+                                scan: HectorScan, pose_hints=None, map_without_matching=None, active=None) -> np.ndarray:
+        """The same on clouds in HBM.  xyz_ptrs / valid_ptrs / take_ptrs: R device addresses each, one block per member (R
+        MotionSync.scans_dev outputs, or slices of one block); member m's row of step k is k rows into its block.  valid_ptrs,
+        take_ptrs or single entries of them may be None (every point valid / every scan taken).  take words are int32, taken
+        iff > 0, take_stride words apart: the `status` field of an MSYNC_RECORD array with MSYNC_RECORD.itemsize // 4."""
+        R = len(self.processors)
+
+        def table(ptrs):
+            if ptrs is None:
+                return None
+            assert len(ptrs) == R, "one device pointer per member"
+            return (C.c_void_p * R)(*[p or None for p in ptrs])
+
+        x, v, t = table(xyz_ptrs), table(valid_ptrs), table(take_ptrs)
+        hints, flags, act = self._per_scan(n_steps, pose_hints, map_without_matching, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_fleet_process_many_clouds_dev(
+            self.h, C.byref(scan), int(n_steps), int(n_points), x, v, t, int(take_stride),
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_synced(self, syncs, laser, ranges, scan: HectorScan, stamps, time_increments, imu_seen=None, odom_seen=None,
+                       pose_hints=None, map_without_matching=None, active=None, n_readings=None):
+        """Raw messages in for R robots: syncs[R] are the members' MotionSync nodes (their IMU and odometry pushed before);
+        ranges [n_steps, R, stride], stamps / time_increments / imu_seen / odom_seen [n_steps, R] -- member m's ScanCallbacks of
+        the call are its steps with active != 0, in step order -> (HECTOR_RECORD[n_steps, R], MSYNC_RECORD[n_steps, R]).  The
+        synchronisation and the de-skew of all members run in 5 launches per call; one host synchronisation."""
+        R = len(self.processors)
+        syncs = list(syncs)
+        assert len(syncs) == R, "one MotionSync per member"
+        hdr = laser if isinstance(laser, MsyncLaser) else MsyncLaser(*[float(v) for v in laser])
+        t = np.ascontiguousarray(stamps, np.float64).reshape(-1, R)
+        n_steps = t.shape[0]
+        ti = np.ascontiguousarray(time_increments, np.float32).reshape(n_steps, R)
+        seen = [None if a is None else np.ascontiguousarray(a, np.int64).reshape(n_steps, R) for a in (imu_seen, odom_seen)]
+        r = np.ascontiguousarray(ranges, dtype=np.float32).reshape(n_steps, R, -1)
+        stride = r.shape[2]
+        nr = stride if n_readings is None else int(n_readings)
+        hints, flags, act = self._per_scan(n_steps, pose_hints, map_without_matching, active)
+        arr = (C.c_void_p * R)(*[s.h for s in syncs])
+        out, rec = np.zeros((n_steps, R), HECTOR_RECORD), np.zeros((n_steps, R), MSYNC_RECORD)
+        self.ctx.check(self.L.lslam_hector_fleet_process_many_synced(
+            self.h, arr, C.byref(scan), C.byref(hdr), n_steps, nr, r.ctypes.data, stride, t.ctypes.data, ti.ctypes.data,
+            None if seen[0] is None else seen[0].ctypes.data, None if seen[1] is None else seen[1].ctypes.data,
+            None if hints is None else hints.ctypes.data, None if flags is None else flags.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data, rec.ctypes.data))
+        return out, rec
+
+    def sync_stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self.ctx.check(self.L.lslam_hector_fleet_sync_stats(self.h, out))
+        return dict(zip(("calls", "launches", "growths", "host_waits"), (int(v) for v in out)))
 
     def stats(self) -> dict:
         out = (C.c_int64 * 6)()

@@ -15,7 +15,7 @@ PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "liblslam_gpu.so"
 SOURCES = ["context.hip", "scan_matcher.hip", "logodds_map.hip", "occupancy_grid.hip", "pool.hip", "deskew.hip",
-           "gmapping_map.hip", "livemap.hip", "raycast.hip", "features.hip", "plicp.hip", "icp.hip", "motion_sync.hip"]
+           "gmapping_map.hip", "livemap.hip", "raycast.hip", "features.hip", "plicp.hip", "icp.hip", "motion_sync.hip", "motion_sync_fleet.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-result"]
 

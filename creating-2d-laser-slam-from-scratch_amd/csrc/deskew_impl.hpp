@@ -79,4 +79,25 @@ int msync_check_scans(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_la
 // the caller has waited for the context's stream: the pinned staging area is free again and the state copy has landed
 void msync_stream_drained(lslam_msync* h);
 
+// csrc/motion_sync.hip for the Hector fleet (lslam_hector_fleet_process_many_synced): the callbacks of R lslam_msync handles
+// in ONE walk, ONE windows, ONE k_deskew_batch and ONE blank launch.  The fleet owns the call's buffers, contiguous over the
+// members (member m's c_m callbacks are rows row0_m .. row0_m + c_m - 1 of every one of them); a handle keeps what outlives
+// a call.  Per-scan host arrays are indexed i = step * R + member; member m's callbacks are its steps with active[i] != 0.
+struct MsyncFleet;
+MsyncFleet* msync_fleet_create(lslam_context* ctx);
+void msync_fleet_destroy(MsyncFleet* mf);
+// Everything that can refuse the call (per member exactly what msync_check_scans refuses; the summed window room; the row
+// count), and the call's layout.  Touches no handle and no device.  The handles are non-null, distinct and of mf's context.
+int msync_fleet_plan(MsyncFleet* mf, lslam_msync* const* syncs, int R, lslam_deskew* deskew, const lslam_msync_laser* laser,
+                     int n_steps, int n_readings, const double* stamps, const float* time_increments, const int64_t* imu_seen,
+                     const int64_t* odom_seen, const uint8_t* active);
+// The planned call on the context's stream, no wait.  -> the clouds, valid flags and records of all rows, and row_of[i] (the
+// row of entry i, -1 where it is not active; valid until the next plan)
+int msync_fleet_enqueue(MsyncFleet* mf, lslam_deskew* deskew, const lslam_msync_laser* laser, const float* ranges, int ranges_stride,
+                        const float** d_xyz, const uint8_t** d_valid, const lslam_msync_record** d_records, const int** row_of);
+int msync_fleet_download(MsyncFleet* mf);  // the records and the R states down, behind everything enqueued (no wait)
+// the caller has waited for the stream: every member handle learns its state; records[i] (may be null) are handed out
+void msync_fleet_finish(MsyncFleet* mf, lslam_msync_record* records);
+void msync_fleet_stats(const MsyncFleet* mf, int64_t out[4]);  // {calls, kernel launches, buffer growths, host waits}
+
 }  // namespace lslam

@@ -1798,6 +1798,10 @@ struct HfScan {
   const int* n_src;     // its count: &st->n_live, or the call's
   const float* ranges;  // ranges form: this scan's readings
   lslam_hector_record* rec;
+  // gated cloud form (k_hfg_*): the scan is taken iff active and (take == nullptr or *take > 0)
+  const int32_t* take;
+  const float* xyz;
+  const uint8_t* valid;  // nullptr: every point is valid
 };
 
 // Entry i of a table the host wrote before the launch and no kernel writes: read through the constant address space, so that
@@ -1854,6 +1858,59 @@ k_hf_apply(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
   const int L = (int)blockIdx.y;
   if (L >= m.ul.n_levels) return;
   hs_apply_block(m.ul, in_device_memory(m.st), in_device_memory(d.pts), in_device_memory(m.cached), L);
+}
+
+// ------------------------------------------------------------------------------------------
+// GATED FLEET chain (lslam_hector_fleet_process_many_clouds[_dev], lslam_hector_fleet_process_many_synced): the gated chain
+// above with the member found in the grid.  Entry (step, member) is taken iff the host's `active` is non-zero AND its device
+// take word says so (HfScan::take null: `active` alone decides) -- the word of a synced call is the status the fleet's walk
+// wrote earlier in the same stream.  k_hfg_cloud_container -> k_hfg_match_* -> k_hf_mark -> k_hf_apply; the last two are the
+// ungated fleet's: an entry that is active but refused on the device has its `updated` cleared by k_hfg_match_* (hg_skip), so
+// hs_mark_block / hs_apply_block return at once, and an entry that is not active returns on `active` as it always did.  The
+// two traps of the single gated chain hold here as well: a skipped match MUST clear `updated`, and a scan that is not taken is
+// NOT an empty container.  A host-inactive entry's record is the host's to write, as in the ungated fleet.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool hfg_word_taken(const int32_t* take) { return hg_taken(in_device_memory(take)); }
+__device__ __forceinline__ bool hfg_taken(const HfScan& d) { return d.active && hfg_word_taken(d.take); }
+
+__global__ void __launch_bounds__(1024)
+k_hfg_cloud_container(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!hfg_taken(d)) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  const ProjectCfg& c = m.pc;
+  const float* __restrict__ xyz = in_device_memory(d.xyz);
+  const uint8_t* __restrict__ valid = in_device_memory(d.valid);
+  hector_compact(c.n, in_device_memory(m.resident), &in_device_memory(m.st)->n_live, [&](int i, float& ox, float& oy) {
+    if (valid && !valid[i]) return false;
+    return hector_cloud_point(c, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ox, oy);
+  });
+}
+
+template <int NT, int PMAX>
+__global__ void __launch_bounds__(NT)
+k_hfg_match_reg(const HfMember* __restrict__ mem, const HfScan* __restrict__ step) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  if (!hfg_word_taken(d.take)) {
+    if (threadIdx.x == 0) hg_skip(in_device_memory(m.st), in_device_memory(d.rec));
+    return;
+  }
+  hs_scan_reg<NT, PMAX>(m.gn, d.sc, in_device_memory(d.pts), in_device_memory(d.n_src), in_device_memory(m.cached), in_device_memory(m.st), in_device_memory(d.rec));
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_hfg_match_fast(const HfMember* __restrict__ mem, const HfScan* __restrict__ step, int pts_in_lds) {
+  const HfScan& d = hf_entry(step, blockIdx.x);
+  if (!d.active) return;
+  const HfMember& m = hf_entry(mem, blockIdx.x);
+  if (!hfg_word_taken(d.take)) {
+    if (threadIdx.x == 0) hg_skip(in_device_memory(m.st), in_device_memory(d.rec));
+    return;
+  }
+  hs_scan_fast<NT>(m.gn, d.sc, in_device_memory(d.pts), in_device_memory(d.n_src), in_device_memory(m.cached), pts_in_lds, in_device_memory(m.st), in_device_memory(d.rec));
 }
 
 float prob_to_logodds(float prob) {  // H/map/GridMapLogOdds.h:151-155 (log() is the double overload)
@@ -4034,8 +4091,14 @@ struct lslam_hector_fleet {
   size_t h_step_cap = 0;
   lslam_hector_record* h_rec = nullptr;
   size_t h_rec_cap = 0;
-  float* h_in = nullptr;  // ranges, or points and then counts
+  float* h_in = nullptr;  // ranges, or points and then counts, or clouds, take words and valid bytes
   size_t h_in_cap = 0;
+  // gated cloud form from the host: valid flags and take words (the clouds go through d_in)
+  DevBuf<uint8_t> d_valid;
+  DevBuf<int32_t> d_take;
+  // synced form: the fleet's own de-skew handle and fleet-wide synchronisation, made by the first synced call
+  lslam_deskew* deskew = nullptr;
+  MsyncFleet* msf = nullptr;
   int64_t n_steps = 0, n_scans = 0, n_updates = 0, n_calls = 0, n_syncs = 0, n_launches = 0;
 };
 
@@ -4053,6 +4116,16 @@ struct HfCall {
   const uint8_t* no_match = nullptr;
   const uint8_t* active = nullptr;
   lslam_hector_record* out = nullptr;
+  // gated cloud form (with `scan`): per entry i = step * R + member, the device addresses of its cloud, its valid flags (null:
+  // all valid) and its take word (null: taken); entries with active == 0 are not read.  take / valid empty: all null
+  bool gated = false;
+  std::vector<const float*> xyz;
+  std::vector<const uint8_t*> valid;
+  std::vector<const int32_t*> take;
+  // synced form: the fleet-wide synchronisation whose walk wrote the take words; its records and states come down with the
+  // processors' and are handed out behind the one wait
+  MsyncFleet* msf = nullptr;
+  lslam_msync_record* sync_out = nullptr;
 };
 
 struct HfWrap { int step, member, level; };  // a key plane whose epochs run out in front of this step
@@ -4066,31 +4139,53 @@ int hf_check(lslam_hector_fleet* f, const char* who, int capacity) {
   return LSLAM_OK;
 }
 
-int hf_run(lslam_hector_fleet* f, const HfCall& c) {
+// Everything of a call that can fail before its first launch: the members' pending updates flushed, and every buffer the call
+// needs.  Doing it twice is doing it once, so the synced form runs it in front of the synchronisation's enqueue -- the nodes
+// must not walk callbacks that the processors then cannot take -- and hf_run runs it again.  *ucap: the points either
+// container of a scan of this call may hold, over all members.
+int hf_reserve(lslam_hector_fleet* f, const HfCall& c, int* ucap, int* max_levels) {
   lslam_context* ctx = f->ctx;
   const int R = (int)f->members.size();
   const size_t total = (size_t)c.n_steps * (size_t)R;
-  const bool ranges_form = c.scan != nullptr;
-  std::vector<int> n_active((size_t)R, 0);  // scans each member takes in this call
+  std::vector<int> n_active((size_t)R, 0);  // scans the host offers each member in this call
   for (size_t i = 0; i < total; i++) n_active[i % (size_t)R] += !c.active || c.active[i];
-  int ucap = 1, max_levels = 1;
+  *ucap = 1;
+  *max_levels = 1;
   for (int m = 0; m < R; m++) {
     lslam_map* map = f->members[m]->map;
-    // (growing a resident container drops what it holds: only for a member whose scans are about to replace it)
-    if (ranges_form && n_active[m]) LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(c.n_readings, 1) + 4));
+    // Growing a resident container drops what it holds: only for a member whose scans may replace it.  In the gated forms
+    // the device may refuse every one of them, and then the member must be what it was: the points move along.
+    if (c.scan && n_active[m]) {
+      const float* old = map->d_scan.p;
+      LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(c.n_readings, 1) + 4));
+      if (c.gated && old && old != map->d_scan.p && map->n_scan > 0)
+        LSLAM_HIP(ctx, hipMemcpyAsync(map->d_scan.p, old, (size_t)2 * map->n_scan * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    }
     int rc = flush_pending(map);  // the matcher reads the float planes; the streamed update is not deferred
     if (rc) return rc;
     int cache_cap = 1;
     rc = hs_reserve_cached(map, c.capacity, &cache_cap);
     if (rc) return rc;
-    ucap = std::max(ucap, cache_cap);
-    max_levels = std::max(max_levels, (int)map->levels.size());
+    *ucap = std::max(*ucap, cache_cap);
+    *max_levels = std::max(*max_levels, (int)map->levels.size());
   }
   LSLAM_HIP(ctx, f->d_step.reserve(total));
   LSLAM_HIP(ctx, f->d_rec.reserve(total));
+  int rc = hs_pinned_reserve(ctx, &f->h_step, &f->h_step_cap, total);
+  if (!rc) rc = hs_pinned_reserve(ctx, &f->h_rec, &f->h_rec_cap, total);
+  return rc;
+}
+
+int hf_run(lslam_hector_fleet* f, const HfCall& c) {
+  lslam_context* ctx = f->ctx;
+  const int R = (int)f->members.size();
+  const size_t total = (size_t)c.n_steps * (size_t)R;
+  const bool ranges_form = c.scan != nullptr;
+  std::vector<int> n_active((size_t)R, 0);  // scans the host offers each member in this call
+  for (size_t i = 0; i < total; i++) n_active[i % (size_t)R] += !c.active || c.active[i];
+  int ucap = 1, max_levels = 1;
   {
-    int rc = hs_pinned_reserve(ctx, &f->h_step, &f->h_step_cap, total);
-    if (!rc) rc = hs_pinned_reserve(ctx, &f->h_rec, &f->h_rec_cap, total);
+    int rc = hf_reserve(f, c, &ucap, &max_levels);
     if (rc) return rc;
   }
   // ---- the member table and the state blocks up: every processor's vectors from its mirror, the cached container's count
@@ -4148,7 +4243,13 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
         d.sc.origo[1] = (float)(double)c.scan->laser_y * f->h_mem[m].pc.scale_to_map;
         d.pts = map->d_scan.p;
         d.n_src = &(f->d_state + m)->n_live;
-        d.ranges = f->d_in.p + i * (size_t)c.n_readings;
+        if (c.gated) {
+          d.xyz = c.xyz[i];
+          d.valid = c.valid.empty() ? nullptr : c.valid[i];
+          d.take = c.take.empty() ? nullptr : c.take[i];
+        } else {
+          d.ranges = f->d_in.p + i * (size_t)c.n_readings;
+        }
       } else {
         d.sc.origo[0] = c.origos ? c.origos[2 * i] : 0.f;
         d.sc.origo[1] = c.origos ? c.origos[2 * i + 1] : 0.f;
@@ -4161,7 +4262,7 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
   LSLAM_HIP(ctx, hipMemcpyAsync(f->d_step.p, f->h_step, total * sizeof(HfScan), hipMemcpyHostToDevice, ctx->stream));
   // the matcher's form from the call's CAPACITY and the members' common LSLAM_GN_THREADS, as the single processor chooses it
   const GnForm form = gn_form_of(f->members[0]->map, c.capacity);
-  const double2* cossin = f->members[0]->map->d_cossin.p;  // (the table follows from the scan geometry alone)
+  const double2* cossin = c.gated ? nullptr : f->members[0]->map->d_cossin.p;  // (the table follows from the scan geometry alone)
   const dim3 ugrid((unsigned)((ucap + 3) / 4), (unsigned)max_levels, (unsigned)R), ublock(256);
   size_t w = 0;
   for (int k = 0; k < c.n_steps; k++) {
@@ -4172,15 +4273,26 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
     }
     const HfMember* mem = f->d_mem;
     const HfScan* step = f->d_step.p + (size_t)k * R;
-    if (ranges_form) {
+    if (c.gated) {
+      launch(ctx, "hfg_cloud_container", k_hfg_cloud_container, dim3(R), dim3(1024), 0, mem, step);
+      f->n_launches++;
+    } else if (ranges_form) {
       launch(ctx, "hf_project", k_hf_project, dim3(R), dim3(1024), 0, mem, step, cossin);
       f->n_launches++;
     }
 #define LSLAM_HF_REG(NT, PMAX) launch(ctx, "hf_match", k_hf_match_reg<NT, PMAX>, dim3(R), dim3(NT), form.lds, mem, step)
 #define LSLAM_HF_FAST(NT) launch(ctx, "hf_match", k_hf_match_fast<NT>, dim3(R), dim3(NT), form.lds, mem, step, form.in_lds)
-    LSLAM_GN_DISPATCH(form, LSLAM_HF_REG, LSLAM_HF_FAST);
+#define LSLAM_HFG_REG(NT, PMAX) launch(ctx, "hfg_match", k_hfg_match_reg<NT, PMAX>, dim3(R), dim3(NT), form.lds, mem, step)
+#define LSLAM_HFG_FAST(NT) launch(ctx, "hfg_match", k_hfg_match_fast<NT>, dim3(R), dim3(NT), form.lds, mem, step, form.in_lds)
+    if (c.gated) {
+      LSLAM_GN_DISPATCH(form, LSLAM_HFG_REG, LSLAM_HFG_FAST);
+    } else {
+      LSLAM_GN_DISPATCH(form, LSLAM_HF_REG, LSLAM_HF_FAST);
+    }
 #undef LSLAM_HF_REG
 #undef LSLAM_HF_FAST
+#undef LSLAM_HFG_REG
+#undef LSLAM_HFG_FAST
     launch(ctx, "hf_mark", k_hf_mark, ugrid, ublock, 0, mem, step);
     launch(ctx, "hf_apply", k_hf_apply, ugrid, ublock, 0, mem, step);
     f->n_launches += 3;
@@ -4191,10 +4303,17 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
   // ---- end of the call: the records and the state blocks down, ONE wait
   LSLAM_HIP(ctx, hipMemcpyAsync(f->h_rec, f->d_rec.p, total * sizeof(lslam_hector_record), hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipMemcpyAsync(f->h_state + R, f->d_state, (size_t)R * sizeof(HsState), hipMemcpyDeviceToHost, ctx->stream));
+  if (c.msf) {
+    int rc = msync_fleet_download(c.msf);
+    if (rc) return rc;
+  }
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   f->n_syncs++;
   f->n_calls++;
   f->n_steps += c.n_steps;
+  if (c.msf) msync_fleet_finish(c.msf, c.sync_out);
+  // the accounting comes from the RECORDS: in the gated forms the device decides whether an active scan is taken
+  std::vector<int> n_taken((size_t)R, 0);
   for (size_t i = 0; i < total; i++) {
     lslam_hector_record& r = f->h_rec[i];
     if (!f->h_step[i].active) {  // a scan that was not taken: all zero but the count
@@ -4202,7 +4321,9 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
       r.n_points = -1;
       continue;
     }
+    if (r.n_points < 0) continue;  // refused on the device: hg_skip wrote its record
     lslam_hector* h = f->members[i % (size_t)R];
+    n_taken[i % (size_t)R]++;
     h->n_scans++;
     h->n_updates += r.updated != 0;
     f->n_scans++;
@@ -4211,7 +4332,7 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
   if (c.out) memcpy(c.out, f->h_rec, total * sizeof(lslam_hector_record));
   // what each member and the host side of its map must know so that lslam_hector_* and lslam_map_* go on working on them
   for (int m = 0; m < R; m++) {
-    if (!n_active[m]) continue;  // (its block came back as it went up)
+    if (!n_taken[m]) continue;  // (its block came back as it went up, but for `updated`, which is the call's)
     lslam_hector* h = f->members[m];
     lslam_map* map = h->map;
     memcpy(&h->mirror, &f->h_state[R + m], kHsPersistWords * 4);
@@ -4297,6 +4418,10 @@ void lslam_hector_fleet_destroy(lslam_hector_fleet* f) {
   f->d_rec.release();
   f->d_in.release();
   f->d_counts.release();
+  f->d_valid.release();
+  f->d_take.release();
+  if (f->deskew) lslam_deskew_destroy(f->deskew);
+  msync_fleet_destroy(f->msf);
   delete f;
 }
 
@@ -4383,6 +4508,183 @@ int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, c
   c.active = active;
   c.out = out;
   return hf_run(f, c);
+}
+
+int lslam_hector_fleet_process_many_clouds_dev(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                               const float* const* xyz_dev, const uint8_t* const* valid_dev,
+                                               const int32_t* const* take_dev, int take_stride, const float* pose_hints,
+                                               const uint8_t* map_without_matching, const uint8_t* active,
+                                               lslam_hector_record* out) {
+  if (!f || n_steps < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  if (!scan || (n_points > 0 && !xyz_dev) || (take_dev && take_stride < 1)) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  const size_t R = f->members.size(), total = (size_t)n_steps * R;
+  std::vector<size_t> n_active(R, 0);
+  for (size_t i = 0; i < total; i++) n_active[i % R] += !active || active[i];
+  if (n_points > 0)
+    for (size_t m = 0; m < R; m++)
+      if (n_active[m] && !xyz_dev[m])
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_clouds_dev: member %zu has scans but no cloud block", m);
+  int rc = hf_check(f, "lslam_hector_fleet_process_many_clouds", n_points);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = n_points;
+  c.scan = scan;
+  c.n_readings = n_points;
+  c.gated = true;
+  c.xyz.assign(total, nullptr);
+  if (valid_dev) c.valid.assign(total, nullptr);
+  if (take_dev) c.take.assign(total, nullptr);
+  for (size_t i = 0; i < total; i++) {  // member m's row of step k: block m + k rows
+    if (active && !active[i]) continue;
+    const size_t k = i / R, m = i % R;
+    c.xyz[i] = n_points > 0 ? xyz_dev[m] + k * (size_t)n_points * 3 : nullptr;
+    if (valid_dev && valid_dev[m]) c.valid[i] = valid_dev[m] + k * (size_t)n_points;
+    if (take_dev && take_dev[m]) c.take[i] = take_dev[m] + k * (size_t)take_stride;
+  }
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.active = active;
+  c.out = out;
+  return hf_run(f, c);
+}
+
+int lslam_hector_fleet_process_many_clouds(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                           const float* xyz, const uint8_t* valid, const uint8_t* take, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out) {
+  if (!f || n_steps < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  if (!scan || (n_points > 0 && !xyz)) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  int rc = hf_check(f, "lslam_hector_fleet_process_many_clouds", n_points);
+  if (rc) return rc;
+  const size_t R = f->members.size(), rows = (size_t)n_steps * R, total = rows * (size_t)n_points;
+  if (total > (size_t)INT32_MAX / 4) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_clouds: call too large");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // pinned: [xyz | take words | valid bytes] (the call ends with a wait: the buffer is never in flight here)
+  const size_t o_take = 3 * total, o_valid = o_take + rows, words = o_valid + (total + 3) / 4;
+  LSLAM_HIP(ctx, f->d_in.reserve(std::max(3 * total, (size_t)1)));
+  if (valid) LSLAM_HIP(ctx, f->d_valid.reserve(std::max(total, (size_t)1)));
+  if (take) LSLAM_HIP(ctx, f->d_take.reserve(rows));
+  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, words);
+  if (rc) return rc;
+  if (total > 0) {
+    memcpy(f->h_in, xyz, 3 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, 3 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (valid) {
+      memcpy(f->h_in + o_valid, valid, total);
+      LSLAM_HIP(ctx, hipMemcpyAsync(f->d_valid.p, f->h_in + o_valid, total, hipMemcpyHostToDevice, ctx->stream));
+    }
+  }
+  if (take) {
+    int32_t* t = reinterpret_cast<int32_t*>(f->h_in + o_take);
+    for (size_t i = 0; i < rows; i++) t[i] = take[i] ? 1 : 0;
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_take.p, t, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = n_points;
+  c.scan = scan;
+  c.n_readings = n_points;
+  c.gated = true;
+  c.xyz.assign(rows, nullptr);
+  if (valid) c.valid.assign(rows, nullptr);
+  if (take) c.take.assign(rows, nullptr);
+  for (size_t i = 0; i < rows; i++) {
+    c.xyz[i] = f->d_in.p + 3 * i * (size_t)n_points;
+    if (valid) c.valid[i] = f->d_valid.p + i * (size_t)n_points;
+    if (take) c.take[i] = f->d_take.p + i;
+  }
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.active = active;
+  c.out = out;
+  return hf_run(f, c);
+}
+
+int lslam_hector_fleet_process_many_synced(lslam_hector_fleet* f, lslam_msync* const* syncs, const lslam_hector_scan* scan,
+                                           const lslam_msync_laser* laser, int n_steps, int n_readings, const float* ranges,
+                                           int ranges_stride, const double* stamps, const float* time_increments,
+                                           const int64_t* imu_seen, const int64_t* odom_seen, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out,
+                                           lslam_msync_record* sync_records) {
+  if (!f || !syncs || n_steps < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  if (!scan || !laser || !ranges || !stamps || !time_increments) return LSLAM_ERR_INVALID_ARGUMENT;
+  const int R = (int)f->members.size();
+  for (int m = 0; m < R; m++)
+    if (!syncs[m]) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  // ---- everything that can refuse the call, before anything is enqueued or any handle changes
+  for (int m = 0; m < R; m++) {
+    if (msync_context(syncs[m]) != ctx)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_synced: member %d's lslam_msync handle belongs to "
+                       "another context than the fleet", m);
+    for (int q = 0; q < m; q++)
+      if (syncs[q] == syncs[m])
+        return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_synced: members %d and %d share one lslam_msync "
+                         "handle; a node belongs to one robot", q, m);
+  }
+  int rc = hf_check(f, "lslam_hector_fleet_process_many_synced", n_readings);
+  if (rc) return rc;
+  if (ranges_stride < n_readings)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_synced: ranges_stride >= n_readings is required");
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  if (!f->deskew) {
+    rc = lslam_deskew_create(ctx, &f->deskew);
+    if (rc) return rc;
+  }
+  if (!f->msf) f->msf = msync_fleet_create(ctx);
+  rc = msync_fleet_plan(f->msf, syncs, R, f->deskew, laser, n_steps, n_readings, stamps, time_increments, imu_seen, odom_seen, active);
+  if (rc) return rc;
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.gated = true;
+  c.active = active;
+  {  // the processors' side of the call is ready before any node walks a callback
+    int ucap = 1, max_levels = 1;
+    rc = hf_reserve(f, c, &ucap, &max_levels);
+    if (rc) return rc;
+  }
+  // ---- the nodes' callbacks of the whole call: rows, walk, windows, ONE de-skew launch, blank -- asynchronous, no wait
+  const float* d_xyz = nullptr;
+  const uint8_t* d_valid = nullptr;
+  const lslam_msync_record* d_recs = nullptr;
+  const int* row_of = nullptr;
+  rc = msync_fleet_enqueue(f->msf, f->deskew, laser, ranges, ranges_stride, &d_xyz, &d_valid, &d_recs, &row_of);
+  if (rc) return rc;
+  static_assert(offsetof(lslam_msync_record, status) == 0, "lslam_msync_record::status is the take word of its callback");
+  const size_t total = (size_t)n_steps * (size_t)R;
+  c.xyz.assign(total, nullptr);
+  c.valid.assign(total, nullptr);
+  c.take.assign(total, nullptr);
+  for (size_t i = 0; i < total; i++) {
+    if (row_of[i] < 0) continue;
+    const size_t row = (size_t)row_of[i];
+    c.xyz[i] = d_xyz + 3 * row * (size_t)n_readings;
+    c.valid[i] = d_valid + row * (size_t)n_readings;
+    c.take[i] = &d_recs[row].status;
+  }
+  c.hints = pose_hints;
+  c.no_match = map_without_matching;
+  c.active = active;
+  c.out = out;
+  c.msf = f->msf;
+  c.sync_out = sync_records;
+  return hf_run(f, c);
+}
+
+int lslam_hector_fleet_sync_stats(const lslam_hector_fleet* f, int64_t out[4]) {
+  if (!f || !out) return LSLAM_ERR_INVALID_ARGUMENT;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (f->msf) msync_fleet_stats(f->msf, out);
+  return LSLAM_OK;
 }
 
 int lslam_hector_fleet_stats(const lslam_hector_fleet* f, int64_t out[6]) {

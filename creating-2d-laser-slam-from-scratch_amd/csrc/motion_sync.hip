@@ -10,278 +10,37 @@
 //                    double, the reference's order; the build passes -ffp-contract=off), computes the odometry increment, and
 //                    writes the DeskewScan record and the IMU planes exactly as k_deskew_batch reads them.
 //   k_msync_blank    zeroes the output rows of queued and refused callbacks (k_deskew_batch cannot skip a scan).
+// The walk's and the windows' bodies live in csrc/motion_sync_impl.hpp: csrc/motion_sync_fleet.hip runs them for the nodes of
+// a whole Hector fleet in one launch each (MsyncFleet below is its host side).
 //
 // Defined where the reference is not: a sample inside the scan with no sample before the scan's start makes :237 read
 // imu_time_[-1] (IMU_NO_LEAD_SAMPLE, refused); more than queueLength = 2000 integrated samples run past imu_time_'s end
 // (IMU_OVERFLOW, refused).  Both are refusals of the IMU step: the odometry step does not run, the IMU pops stay made.
 #include <cmath>
 
-#include "deskew_impl.hpp"
+#include "motion_sync_impl.hpp"
 
 using namespace lslam;
 
 namespace {
 
-constexpr int kQueueLength = LSLAM_MSYNC_QUEUE_LENGTH;
-
-// the node's members that outlive a callback (all message indices are GLOBAL: counted since create / reset)
-struct MsyncState {
-  long long imu_front, odom_front;  // imu_queue_.front() / odom_queue_.front()
-  long long start_odom, end_odom;   // start_odom_msg_ / end_odom_msg_; -1: default-constructed (stamp 0, identity)
-  double queued_stamp;              // laser_queue_'s one waiting scan (its ranges are row 0 of the handle's rows)
-  float queued_tinc;
-  int has_queued;
-  long long n_corrected, n_refused;
-};
-
-// what the walk leaves for the windows kernel, per callback
-struct MsyncWalk {
-  long long imu_lo, imu_stop, imu_lead;  // the IMU loop of :207-243 runs over [imu_lo, imu_stop); imu_lead: sample 0 or -1
-};
-
-struct MsyncQueues {
-  const double* imu;   // planes stamp, wx, wy, wz of imu_cap doubles; entry of message g at g - imu_base
-  const double* odom;  // planes stamp, x, y, z, qx, qy, qz, qw of odom_cap doubles
-  long long imu_base, odom_base;
-  size_t imu_cap, odom_cap;
-};
-
-// Pop literally (:191-197, :266-272): advance while stamp[front] < lim, no lower bound.  Wave-uniform.
-__device__ __forceinline__ long long pop_front(const double* stamp, long long base, long long front, long long seen, double lim,
-                                               int lane) {
-  while (front < seen) {
-    const long long i = front + lane;
-    const bool stop = i < seen && !(stamp[i - base] < lim);
-    const unsigned long long b = __ballot(stop);
-    if (b) return front + (__ffsll((long long)b) - 1);
-    front = min(front + 64, seen);
-  }
-  return front;
-}
-
 __global__ void __launch_bounds__(64)
 k_msync_walk(MsyncState* __restrict__ state, MsyncQueues q, int use_imu, int use_odom, int scan_count, int n_msgs,
              const double* __restrict__ stamps, const float* __restrict__ tincs, const long long* __restrict__ imu_seen,
              const long long* __restrict__ odom_seen, lslam_msync_record* __restrict__ recs, MsyncWalk* __restrict__ walks) {
-  const int lane = threadIdx.x;
-  MsyncState st = *state;  // (every lane holds the same copy)
-  const double* it = q.imu;
-  const double* ot = q.odom;
-  for (int k = 0; k < n_msgs; k++) {
-    lslam_msync_record r;
-    r.status = LSLAM_MSYNC_QUEUED; r.n_imu = 0;
-    r.scan_time_start = 0.0; r.time_increment = 0.0;
-    r.start_odom_time = 0.0; r.end_odom_time = 0.0;
-    r.odom_incre[0] = r.odom_incre[1] = r.odom_incre[2] = 0.f; r.pad = 0.f;
-    MsyncWalk w;
-    w.imu_lo = w.imu_stop = 0; w.imu_lead = -1;
-    const double new_stamp = stamps[k];
-    const float new_tinc = tincs[k];
-    if (st.has_queued) {  // CacheLaserScan (:142-156): the scan queued by the previous callback is the current one
-      const double start = st.queued_stamp;
-      const double tinc = (double)st.queued_tinc;
-      const double end = start + tinc * (double)(scan_count - 1);
-      r.scan_time_start = start; r.time_increment = tinc;
-      int status = LSLAM_MSYNC_CORRECTED;
-      if (use_imu) {  // PruneImuDeque
-        const long long seen = imu_seen[k];
-        long long f = st.imu_front;
-        if (f >= seen || it[f - q.imu_base] > start || it[seen - 1 - q.imu_base] < end) {  // :182-188
-          status = LSLAM_MSYNC_WAIT_IMU;
-        } else {
-          f = pop_front(it, q.imu_base, f, seen, start - 0.1, lane);
-          st.imu_front = f;
-          if (f >= seen) {  // :199-200
-            status = LSLAM_MSYNC_WAIT_IMU;
-          } else {  // where the loop of :207-243 stops, its sample 0, and how many samples it keeps
-            long long lead = -1, first_in = -1, stop = seen;
-            int kept_in = 0;
-            for (long long c = f; c < seen; c += 64) {
-              const long long i = c + lane;
-              const bool have = i < seen;
-              const double t = have ? it[i - q.imu_base] : 0.0;
-              const bool pre = have && t < start;            // :212
-              const bool late = have && !pre && t > end;     // :227
-              const unsigned long long bl = __ballot(late);
-              const unsigned long long before = bl ? ((1ull << (__ffsll((long long)bl) - 1)) - 1ull) : ~0ull;
-              const unsigned long long bp = __ballot(pre) & before;
-              const unsigned long long bi = __ballot(have && !pre && !late) & before;
-              if (lead < 0 && bp) lead = c + (__ffsll((long long)bp) - 1);
-              if (first_in < 0 && bi) first_in = c + (__ffsll((long long)bi) - 1);
-              kept_in = min(kept_in + __popcll(bi), kQueueLength + 1);
-              if (bl) {
-                stop = c + (__ffsll((long long)bl) - 1);
-                break;
-              }
-            }
-            w.imu_lo = f; w.imu_stop = stop; w.imu_lead = lead;
-            const int kept = kept_in + (lead >= 0 ? 1 : 0);
-            r.n_imu = kept;
-            if (kept_in > 0 && (lead < 0 || first_in < lead)) status = LSLAM_MSYNC_IMU_NO_LEAD_SAMPLE;
-            else if (kept > kQueueLength) status = LSLAM_MSYNC_IMU_OVERFLOW;
-            if (status != LSLAM_MSYNC_CORRECTED) r.n_imu = 0;
-          }
-        }
-      }
-      if (use_odom && status == LSLAM_MSYNC_CORRECTED) {  // PruneOdomDeque
-        const long long seen = odom_seen[k];
-        long long f = st.odom_front;
-        if (f >= seen || ot[f - q.odom_base] > start || ot[seen - 1 - q.odom_base] < end) {  // :257-263
-          status = LSLAM_MSYNC_WAIT_ODOM;
-        } else {
-          f = pop_front(ot, q.odom_base, f, seen, start - 0.1, lane);
-          st.odom_front = f;
-          if (f >= seen) {  // :274-275
-            status = LSLAM_MSYNC_WAIT_ODOM;
-          } else {  // :280-296: the last message before the start, the last one up to the end; what finds none stays
-            for (long long c = f; c < seen; c += 64) {
-              const long long i = c + lane;
-              const bool have = i < seen;
-              const double t = have ? ot[i - q.odom_base] : 0.0;
-              const bool pre = have && t < start;               // :284
-              const bool late = have && !pre && !(t <= end);    // :290-295
-              const unsigned long long bl = __ballot(late);
-              const unsigned long long before = bl ? ((1ull << (__ffsll((long long)bl) - 1)) - 1ull) : ~0ull;
-              const unsigned long long bp = __ballot(pre) & before;
-              const unsigned long long bi = __ballot(have && !pre && !late) & before;
-              if (bp) st.start_odom = c + (63 - __clzll((long long)bp));
-              if (bi) st.end_odom = c + (63 - __clzll((long long)bi));
-              if (bl) break;
-            }
-            r.start_odom_time = st.start_odom >= 0 ? ot[st.start_odom - q.odom_base] : 0.0;  // :301-302
-            r.end_odom_time = st.end_odom >= 0 ? ot[st.end_odom - q.odom_base] : 0.0;
-          }
-        }
-      }
-      if (status != LSLAM_MSYNC_CORRECTED) r.n_imu = 0;
-      r.status = status;
-      if (status == LSLAM_MSYNC_CORRECTED) st.n_corrected++;
-      else st.n_refused++;
-    }
-    st.has_queued = 1;
-    st.queued_stamp = new_stamp;
-    st.queued_tinc = new_tinc;
-    r.imu_front = st.imu_front; r.odom_front = st.odom_front;
-    r.start_odom_index = st.start_odom; r.end_odom_index = st.end_odom;
-    if (lane == 0) {
-      recs[k] = r;
-      walks[k] = w;
-    }
-  }
-  if (lane == 0) *state = st;
-}
-
-// tf::Matrix3x3(q).getRPY (setRotation + getEulerYPR, solution 1; LinearMath/Matrix3x3.h), double
-__device__ __forceinline__ void quat_rpy(double x, double y, double z, double w, double& roll, double& pitch, double& yaw) {
-  const double d = x * x + y * y + z * z + w * w;
-  const double s = 2.0 / d;
-  const double xs = x * s, ys = y * s, zs = z * s;
-  const double wx = w * xs, wy = w * ys, wz = w * zs;
-  const double xx = x * xs, xy = x * ys, xz = x * zs;
-  const double yy = y * ys, yz = y * zs, zz = z * zs;
-  const double m00 = 1.0 - (yy + zz), m10 = xy + wz, m20 = xz - wy, m21 = yz + wx, m22 = 1.0 - (xx + yy);
-  if (fabs(m20) >= 1.0) {
-    yaw = 0.0;
-    roll = atan2(m21, m22);
-    pitch = m20 < 0 ? M_PI / 2.0 : -M_PI / 2.0;
-  } else {
-    pitch = -asin(m20);
-    roll = atan2(m21 / cos(pitch), m22 / cos(pitch));
-    yaw = atan2(m10 / cos(pitch), m00 / cos(pitch));
-  }
-}
-
-// pcl::getTransformation of an odometry message's pose (:307-325); g < 0: the default-constructed message
-__device__ __forceinline__ Aff3 odom_transform(const MsyncQueues& q, long long g) {
-  double p[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  if (g >= 0)
-    for (int a = 0; a < 7; a++) p[a] = q.odom[(size_t)(a + 1) * q.odom_cap + (size_t)(g - q.odom_base)];
-  double roll, pitch, yaw;
-  quat_rpy(p[3], p[4], p[5], p[6], roll, pitch, yaw);
-  return get_transformation((float)p[0], (float)p[1], (float)p[2], (float)roll, (float)pitch, (float)yaw);
+  msync_walk_body(state, q, use_imu, use_odom, scan_count, n_msgs, stamps, tincs, imu_seen, odom_seen, recs, walks);
 }
 
 __global__ void __launch_bounds__(64)
 k_msync_windows(MsyncQueues q, int use_imu, int use_odom, lslam_msync_record* recs, const MsyncWalk* __restrict__ walks,
                 const int* __restrict__ win_first, DeskewScan* __restrict__ scans, double* win, int win_plane) {
-  const int k = blockIdx.x, lane = threadIdx.x;
-  const lslam_msync_record r = recs[k];
-  const MsyncWalk w = walks[k];
-  const int first = win_first[k];
-  double* T = win + first;
-  DeskewScan s;
-  s.t0 = r.scan_time_start; s.dt = r.time_increment;
-  s.odom_t0 = 0.0; s.odom_t1 = 0.0;
-  s.odom_dx = s.odom_dy = s.odom_dz = 0.f;
-  s.use_imu = 0; s.use_odom = 0;
-  s.imu_first = first; s.n_imu = 0; s.pad = 0;
-  if (r.status != LSLAM_MSYNC_CORRECTED) {  // k_deskew_batch still runs on this row: a record that reads nothing
-    if (lane == 0) scans[k] = s;
-    return;
-  }
-  if (use_imu) {
-    const double start = r.scan_time_start;
-    int pos = 0;
-    if (w.imu_lead >= 0) {  // :215-222: the first sample before the start is sample 0, rotation 0
-      if (lane == 0) T[0] = q.imu[w.imu_lead - q.imu_base];
-      if (lane < 3) T[(size_t)(lane + 1) * win_plane] = 0.0;
-      pos = 1;
-    }
-    for (long long c = w.imu_lo; c < w.imu_stop; c += 64) {  // the kept samples, compacted in order (the rot planes hold
-      const long long i = c + lane;                          // the angular velocities until they are integrated below)
-      double t = 0.0;
-      bool keep = false;
-      if (i < w.imu_stop) {
-        t = q.imu[i - q.imu_base];
-        keep = !(t < start);  // later samples before the start are skipped (:223)
-      }
-      const unsigned long long b = __ballot(keep);
-      if (keep) {
-        const int at = pos + __popcll(b & ((1ull << lane) - 1ull));
-        T[at] = t;
-        for (int a = 1; a < 4; a++) T[(size_t)a * win_plane + at] = q.imu[(size_t)a * q.imu_cap + (size_t)(i - q.imu_base)];
-      }
-      pos += __popcll(b);
-    }
-    if (pos == 0) {  // no sample in reach: current_imu_index_ = -1, ComputeRotation reads the reset arrays' entry 0
-      if (lane < 4) T[(size_t)lane * win_plane] = 0.0;
-    }
-    __syncthreads();  // (one wave: the samples the other lanes wrote are visible)
-    if (lane < 3 && pos > 1) {  // :237-241, one lane per axis
-      double* R = T + (size_t)(lane + 1) * win_plane;
-      double rot = 0.0, t_prev = T[0];
-      for (int i = 1; i < pos; i++) {
-        const double t = T[i];
-        const double time_diff = t - t_prev;
-        rot = rot + R[i] * time_diff;
-        R[i] = rot;
-        t_prev = t;
-      }
-    }
-    s.use_imu = 1;
-    s.n_imu = max(pos, 1);
-  }
-  if (use_odom && lane == 0) {  // :304-334
-    const Aff3 begin = odom_transform(q, r.start_odom_index);
-    const Aff3 end = odom_transform(q, r.end_odom_index);
-    const Aff3 bt = mul(inverse(begin), end);
-    s.use_odom = 1;
-    s.odom_t0 = r.start_odom_time; s.odom_t1 = r.end_odom_time;
-    s.odom_dx = bt.t[0]; s.odom_dy = bt.t[1]; s.odom_dz = bt.t[2];
-    recs[k].odom_incre[0] = bt.t[0]; recs[k].odom_incre[1] = bt.t[1]; recs[k].odom_incre[2] = bt.t[2];
-  }
-  if (lane == 0) scans[k] = s;
+  msync_windows_body(q, use_imu, use_odom, (int)blockIdx.x, recs, walks, win_first, scans, win, win_plane);
 }
 
+// (the fleet's records are contiguous over its members: one launch of this kernel over all rows serves it as it stands)
 __global__ void __launch_bounds__(256)
 k_msync_blank(const lslam_msync_record* __restrict__ recs, int n, float* __restrict__ out_xyz, uint8_t* __restrict__ valid) {
-  const int k = blockIdx.y;
-  if (recs[k].status == LSLAM_MSYNC_CORRECTED) return;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float* o = out_xyz + ((size_t)k * n + i) * 3;
-  o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
-  valid[(size_t)k * n + i] = 0;
+  msync_blank_body(recs, n, (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x), out_xyz, valid);
 }
 
 }  // namespace
@@ -323,6 +82,7 @@ struct lslam_msync {
   // the last call, for read_windows
   int last_n = 0, last_win_plane = 0;
   std::vector<int> last_win_first;
+  bool last_in_fleet = false;  // the last call was a fleet's: its windows live in the fleet's buffer (read_windows refuses)
   int64_t n_callbacks = 0, n_launches = 0, n_growths = 0, n_waits = 0;
 };
 
@@ -517,6 +277,7 @@ int ms_enqueue(lslam_msync* h, lslam_deskew* deskew, const lslam_msync_laser* la
   h->last_n = n_msgs;
   h->last_win_plane = win_plane;
   h->last_win_first.assign(u_first, u_first + n_msgs);
+  h->last_in_fleet = false;
   return LSLAM_OK;
 }
 
@@ -536,6 +297,7 @@ int ms_reset_state(lslam_msync* h) {
   h->last_n = 0;
   h->last_win_plane = 0;
   h->last_win_first.clear();
+  h->last_in_fleet = false;
   h->n_callbacks = h->n_launches = 0;
   return LSLAM_OK;
 }
@@ -553,6 +315,285 @@ int lslam::msync_check_scans(lslam_msync* h, lslam_deskew* deskew, const lslam_m
 void lslam::msync_stream_drained(lslam_msync* h) {
   h->stage_used = 0;
   ms_poll_state(h);
+}
+
+// ------------------------------------------------------------------------------------------
+// MsyncFleet: the buffers of one fleet call and its plan.  Launches per call: k_msync_fleet_rows / _walk / _windows
+// (csrc/motion_sync_fleet.hip), k_deskew_batch, k_msync_blank -- kFleetLaunches, whatever R and the number of steps are (a new scan geometry adds the de-skew's angle table).
+// ------------------------------------------------------------------------------------------
+struct lslam::MsyncFleet {
+  lslam_context* ctx = nullptr;
+  DevBuf<unsigned char> d_meta, d_work;  // [member table | stamps | imu_seen | odom_seen | win_first | tincs]; [scans | records | walks]
+  DevBuf<double> d_win;
+  DevBuf<float> d_rows, d_xyz;           // d_rows: the N rows of the call, then one tail row per member
+  DevBuf<uint8_t> d_valid;
+  DevBuf<MsyncState> d_states;
+  unsigned char* h_up = nullptr;         // pinned, what goes up: the meta block, then the ranges
+  unsigned char* h_down = nullptr;       // pinned, what comes down: the records, then the states
+  size_t h_up_cap = 0, h_down_cap = 0;
+  // the plan of the call
+  std::vector<lslam_msync*> syncs;
+  int R = 0, n = 0, n_steps = 0, N = 0, max_cb = 0, win_plane = 0;
+  std::vector<int> n_cb, row0, row_of, win_first;
+  std::vector<double> stamps;
+  std::vector<float> tincs;
+  std::vector<long long> iseen, oseen;
+  int64_t n_calls = 0, n_launches = 0, n_growths = 0, n_waits = 0;
+};
+
+namespace {
+
+constexpr int kFleetLaunches = 5;
+
+template <typename T>
+int mf_reserve(MsyncFleet* mf, DevBuf<T>& b, size_t n) {
+  if (n <= b.cap) return LSLAM_OK;
+  LSLAM_HIP(mf->ctx, b.reserve(n));
+  mf->n_growths++;
+  return LSLAM_OK;
+}
+
+int mf_pinned(MsyncFleet* mf, unsigned char** p, size_t* cap, size_t bytes) {  // (every call ends with a wait: never in flight here)
+  if (bytes <= *cap) return LSLAM_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = bytes + bytes / 4 + 256;
+  LSLAM_HIP(mf->ctx, hipHostMalloc((void**)p, want, hipHostMallocDefault));
+  *cap = want;
+  mf->n_growths++;
+  return LSLAM_OK;
+}
+
+}  // namespace
+
+MsyncFleet* lslam::msync_fleet_create(lslam_context* ctx) {
+  MsyncFleet* mf = new MsyncFleet();
+  mf->ctx = ctx;
+  return mf;
+}
+
+void lslam::msync_fleet_destroy(MsyncFleet* mf) {
+  if (!mf) return;
+  if (mf->h_up) (void)hipHostFree(mf->h_up);
+  if (mf->h_down) (void)hipHostFree(mf->h_down);
+  mf->d_meta.release();
+  mf->d_work.release();
+  mf->d_win.release();
+  mf->d_rows.release();
+  mf->d_xyz.release();
+  mf->d_valid.release();
+  mf->d_states.release();
+  delete mf;
+}
+
+int lslam::msync_fleet_plan(MsyncFleet* mf, lslam_msync* const* syncs, int R, lslam_deskew* deskew, const lslam_msync_laser* laser,
+                            int n_steps, int n_readings, const double* stamps, const float* time_increments,
+                            const int64_t* imu_seen, const int64_t* odom_seen, const uint8_t* active) {
+  lslam_context* ctx = mf->ctx;
+  const size_t total = (size_t)n_steps * (size_t)R;
+  mf->syncs.assign(syncs, syncs + R);
+  mf->R = R; mf->n = n_readings; mf->n_steps = n_steps;
+  mf->n_cb.assign((size_t)R, 0);
+  mf->row0.assign((size_t)R, 0);
+  mf->row_of.assign(total, -1);
+  for (size_t i = 0; i < total; i++) mf->n_cb[i % (size_t)R] += !active || active[i];
+  size_t N = 0;
+  mf->max_cb = 0;
+  for (int m = 0; m < R; m++) {
+    mf->row0[m] = (int)N;
+    N += (size_t)mf->n_cb[m];
+    mf->max_cb = std::max(mf->max_cb, mf->n_cb[m]);
+  }
+  if (N > 65535)  // k_deskew_batch and k_msync_blank take a scan per grid row
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_synced: at most 65535 scan callbacks per call over "
+                     "all members (got %zu); make shorter calls", N);
+  mf->N = (int)N;
+  mf->stamps.assign(N, 0.0);
+  mf->tincs.assign(N, 0.f);
+  mf->iseen.assign(N, 0);
+  mf->oseen.assign(N, 0);
+  mf->win_first.assign(N, 0);
+  std::vector<int64_t> is, os;
+  long long room = 0;
+  for (int m = 0; m < R; m++) {  // member-major: member m's callbacks in step order
+    const int c = mf->n_cb[m];
+    if (c == 0) continue;
+    lslam_msync* h = syncs[m];
+    const int r0 = mf->row0[m];
+    is.assign((size_t)c, 0);
+    os.assign((size_t)c, 0);
+    int j = 0;
+    for (int k = 0; k < n_steps; k++) {
+      const size_t i = (size_t)k * R + m;
+      if (active && !active[i]) continue;
+      mf->row_of[i] = r0 + j;
+      mf->stamps[r0 + j] = stamps[i];
+      mf->tincs[r0 + j] = time_increments[i];
+      is[j] = imu_seen ? imu_seen[i] : (int64_t)h->imu.count;
+      os[j] = odom_seen ? odom_seen[i] : (int64_t)h->odom.count;
+      j++;
+    }
+    const void* const callers = h;  // stands for the device pointers, which ms_check only compares with NULL
+    int rc = ms_check(h, deskew, laser, c, n_readings, callers, n_readings, mf->stamps.data() + r0, mf->tincs.data() + r0, is.data(),
+                      os.data(), callers, callers);
+    if (rc) return rc;
+    for (j = 0; j < c; j++) {  // every callback owns room for the most samples its window can hold, as in ms_enqueue
+      mf->iseen[r0 + j] = is[j];
+      mf->oseen[r0 + j] = os[j];
+      if (room > INT_MAX)
+        return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_synced: the IMU windows of the call need more than "
+                         "INT_MAX samples of room; make shorter calls");
+      mf->win_first[r0 + j] = (int)room;
+      room += h->use_imu ? std::max<long long>(1, std::min<long long>(kQueueLength, is[j] - h->imu.base)) : 1;
+    }
+  }
+  if (room > INT_MAX)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_synced: the IMU windows of the call need more than "
+                     "INT_MAX samples of room; make shorter calls");
+  mf->win_plane = (int)room;
+  return LSLAM_OK;
+}
+
+int lslam::msync_fleet_enqueue(MsyncFleet* mf, lslam_deskew* deskew, const lslam_msync_laser* laser, const float* ranges,
+                               int ranges_stride, const float** d_xyz, const uint8_t** d_valid,
+                               const lslam_msync_record** d_records, const int** row_of) {
+  lslam_context* ctx = mf->ctx;
+  const int R = mf->R, N = mf->N;
+  const size_t n = (size_t)mf->n, Nz = (size_t)N;
+  *row_of = mf->row_of.data();
+  // ---- every buffer first (an allocation may wait for the device, but enqueues nothing)
+  const size_t o_mem = 0, o_stamps = o_mem + (size_t)R * sizeof(MsyncMember), o_iseen = o_stamps + Nz * 8, o_oseen = o_iseen + Nz * 8,
+               o_first = o_oseen + Nz * 8, o_tinc = o_first + Nz * 4, meta_bytes = (o_tinc + Nz * 4 + 7) / 8 * 8;
+  const size_t o_scans = 0, o_recs = o_scans + Nz * sizeof(DeskewScan), o_walks = o_recs + Nz * sizeof(lslam_msync_record),
+               work_bytes = o_walks + Nz * sizeof(MsyncWalk);
+  const size_t rows = Nz + (size_t)R, rec_bytes = Nz * sizeof(lslam_msync_record);
+  int rc;
+  if ((rc = mf_reserve(mf, mf->d_meta, meta_bytes)) || (rc = mf_reserve(mf, mf->d_work, std::max<size_t>(work_bytes, 8))) ||
+      (rc = mf_reserve(mf, mf->d_win, (size_t)4 * std::max(mf->win_plane, 1))) || (rc = mf_reserve(mf, mf->d_rows, rows * n)) ||
+      (rc = mf_reserve(mf, mf->d_xyz, std::max<size_t>(3 * Nz * n, 1))) || (rc = mf_reserve(mf, mf->d_valid, std::max<size_t>(Nz * n, 1))) ||
+      (rc = mf_reserve(mf, mf->d_states, (size_t)R)) ||
+      (rc = mf_pinned(mf, &mf->h_up, &mf->h_up_cap, meta_bytes + rows * n * sizeof(float))) ||
+      (rc = mf_pinned(mf, &mf->h_down, &mf->h_down_cap, rec_bytes + (size_t)R * sizeof(MsyncState))))
+    return rc;
+  *d_xyz = mf->d_xyz.p;
+  *d_valid = mf->d_valid.p;
+  *d_records = reinterpret_cast<const lslam_msync_record*>(mf->d_work.p + o_recs);
+  // Every member with callbacks owns a queued-scan row of at least n floats, which k_msync_fleet_rows reads and writes in
+  // full.  A handle that has a scan queued has rows of this n already (ms_check: n is its scan_count, and every call
+  // reserves two rows or more).  One that has none -- its first scan ever, or its first after lslam_msync_reset, which
+  // forgets scan_count but keeps the buffers, possibly of a SHORTER scan -- gets a row that is long enough and zero (it is
+  // never used: has_queued is 0), as the handle's own calls make it.
+  for (int m = 0; m < R; m++) {
+    lslam_msync* h = mf->syncs[m];
+    if (!mf->n_cb[m] || h->d_rows.cap >= n) continue;
+    if ((rc = ms_reserve(h, h->d_rows, 2 * n))) return rc;
+    LSLAM_HIP(ctx, hipMemsetAsync(h->d_rows.p, 0, n * sizeof(float), ctx->stream));
+  }
+  mf->n_calls++;
+  if (N == 0) return LSLAM_OK;  // nobody has a callback: nothing to run
+  for (int m = 0; m < R; m++)
+    if (mf->n_cb[m]) ms_poll_state(mf->syncs[m]);
+  // ---- up: the member table and the call's small inputs in one copy, the ranges in another
+  unsigned char* up = mf->h_up;
+  MsyncMember* u_mem = reinterpret_cast<MsyncMember*>(up + o_mem);
+  for (int m = 0; m < R; m++) {
+    lslam_msync* h = mf->syncs[m];
+    MsyncMember e{};
+    e.n_cb = mf->n_cb[m];
+    e.row0 = mf->row0[m];
+    if (e.n_cb) {
+      e.state = h->d_state.p;
+      e.queued_row = h->d_rows.p;
+      e.q.imu = h->imu.buf[h->imu.live].p; e.q.odom = h->odom.buf[h->odom.live].p;
+      e.q.imu_base = h->imu.base; e.q.odom_base = h->odom.base;
+      e.q.imu_cap = h->imu.cap; e.q.odom_cap = h->odom.cap;
+      e.use_imu = h->use_imu; e.use_odom = h->use_odom;
+    }
+    u_mem[m] = e;
+  }
+  memcpy(up + o_stamps, mf->stamps.data(), Nz * 8);
+  memcpy(up + o_iseen, mf->iseen.data(), Nz * 8);
+  memcpy(up + o_oseen, mf->oseen.data(), Nz * 8);
+  memcpy(up + o_first, mf->win_first.data(), Nz * 4);
+  memcpy(up + o_tinc, mf->tincs.data(), Nz * 4);
+  LSLAM_HIP(ctx, hipMemcpyAsync(mf->d_meta.p, up, meta_bytes, hipMemcpyHostToDevice, ctx->stream));
+  // row row0 + j, j >= 1, is member m's message j - 1; its last message is tail row m; row row0 is k_msync_fleet_rows'
+  float* u_rows = reinterpret_cast<float*>(up + meta_bytes);
+  for (size_t i = 0; i < mf->row_of.size(); i++) {
+    const int row = mf->row_of[i];
+    if (row < 0) continue;
+    const int m = (int)(i % (size_t)R);
+    const bool last = row == mf->row0[m] + mf->n_cb[m] - 1;
+    memcpy(u_rows + (last ? Nz + (size_t)m : (size_t)row + 1) * n, ranges + i * (size_t)ranges_stride, n * sizeof(float));
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(mf->d_rows.p, u_rows, rows * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  const MsyncMember* d_mem = reinterpret_cast<const MsyncMember*>(mf->d_meta.p + o_mem);
+  DeskewScan* d_scans = reinterpret_cast<DeskewScan*>(mf->d_work.p + o_scans);
+  lslam_msync_record* d_recs = reinterpret_cast<lslam_msync_record*>(mf->d_work.p + o_recs);
+  MsyncWalk* d_walks = reinterpret_cast<MsyncWalk*>(mf->d_work.p + o_walks);
+  msync_fleet_launch_rows(ctx, d_mem, R, (int)n, mf->d_rows.p, mf->d_rows.p + Nz * n);
+  msync_fleet_launch_walk(ctx, d_mem, R, (int)n, (const double*)(mf->d_meta.p + o_stamps), (const float*)(mf->d_meta.p + o_tinc),
+                          (const long long*)(mf->d_meta.p + o_iseen), (const long long*)(mf->d_meta.p + o_oseen), d_recs, d_walks,
+                          mf->d_states.p);
+  msync_fleet_launch_windows(ctx, d_mem, R, mf->max_cb, d_recs, d_walks, (const int*)(mf->d_meta.p + o_first), d_scans, mf->d_win.p,
+                             mf->win_plane);
+  const float geom[4] = {laser->angle_min, laser->angle_increment, laser->range_min, laser->range_max};
+  rc = deskew_launch_records(deskew, N, (int)n, mf->d_rows.p, (int)n, geom, d_scans, mf->d_win.p, mf->win_plane, mf->d_xyz.p,
+                             mf->d_valid.p);
+  if (rc) return rc;
+  launch(ctx, "msync_blank", k_msync_blank, dim3((unsigned)((n + 255) / 256), (unsigned)N), dim3(256), 0,
+         (const lslam_msync_record*)d_recs, (int)n, mf->d_xyz.p, mf->d_valid.p);
+  mf->n_launches += kFleetLaunches;
+  LSLAM_HIP(ctx, hipGetLastError());
+  // what each handle's own bookkeeping must know (its launches do not move: the fleet counts those)
+  for (int m = 0; m < R; m++) {
+    const int c = mf->n_cb[m];
+    if (!c) continue;
+    lslam_msync* h = mf->syncs[m];
+    const int last = mf->row0[m] + c - 1;
+    h->scan_count = (int)n;
+    h->imu.seen = mf->iseen[last];
+    h->odom.seen = mf->oseen[last];
+    h->n_callbacks += c;
+    h->last_n = 0;
+    h->last_win_plane = 0;
+    h->last_win_first.clear();
+    h->last_in_fleet = true;
+  }
+  return LSLAM_OK;
+}
+
+int lslam::msync_fleet_download(MsyncFleet* mf) {
+  lslam_context* ctx = mf->ctx;
+  if (mf->N == 0) return LSLAM_OK;
+  const size_t Nz = (size_t)mf->N, rec_bytes = Nz * sizeof(lslam_msync_record);
+  LSLAM_HIP(ctx, hipMemcpyAsync(mf->h_down, mf->d_work.p + Nz * sizeof(DeskewScan), rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipMemcpyAsync(mf->h_down + rec_bytes, mf->d_states.p, (size_t)mf->R * sizeof(MsyncState), hipMemcpyDeviceToHost,
+                                ctx->stream));
+  return LSLAM_OK;
+}
+
+void lslam::msync_fleet_finish(MsyncFleet* mf, lslam_msync_record* records) {
+  mf->n_waits++;
+  const lslam_msync_record* recs = reinterpret_cast<const lslam_msync_record*>(mf->h_down);
+  const MsyncState* states = reinterpret_cast<const MsyncState*>(mf->h_down + (size_t)mf->N * sizeof(lslam_msync_record));
+  for (int m = 0; m < mf->R; m++) {
+    if (!mf->n_cb[m]) continue;
+    lslam_msync* h = mf->syncs[m];
+    h->known = states[m];  // newer than any copy of the handle's own that was in flight, which has landed too
+    h->state_in_flight = false;
+    h->stage_used = 0;
+  }
+  if (!records) return;
+  for (size_t i = 0; i < mf->row_of.size(); i++) {
+    if (mf->row_of[i] < 0) memset(&records[i], 0, sizeof records[i]);
+    else records[i] = recs[mf->row_of[i]];
+  }
+}
+
+void lslam::msync_fleet_stats(const MsyncFleet* mf, int64_t out[4]) {
+  out[0] = mf->n_calls; out[1] = mf->n_launches; out[2] = mf->n_growths; out[3] = mf->n_waits;
 }
 
 extern "C" {
@@ -705,6 +746,10 @@ int lslam_msync_read_windows(lslam_msync* h, int32_t* imu_first, double* imu_tim
   if (!h || !imu_first || capacity < 0) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_context* ctx = h->ctx;
   imu_first[0] = 0;
+  if (h->last_in_fleet)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_msync_read_windows: the handle's last call was a fleet's "
+                     "(lslam_hector_fleet_process_many_synced), whose windows live in the fleet's buffer; they are readable "
+                     "again after the handle's next call of its own");
   if (h->last_n == 0) return LSLAM_OK;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));

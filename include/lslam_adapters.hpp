@@ -632,6 +632,33 @@ class HectorSlamFleetGpu {
     check(lslam_hector_fleet_process_many(h_, &scan, nSteps, nReadings, ranges, rangesStride, poseHints, mapWithoutMatching,
                                           active, records));
   }
+  // The gated forms (HectorSlamProcessorGpu::updateManyClouds / updateManyCloudsDev / updateManySynced for size() robots per
+  // launch); every per-scan array indexed step * size() + member.  An entry is taken iff active (nullptr = all) and its take
+  // flag (nullptr = all) say so; one that is not changes nothing of its member, its record is zero with n_points = -1.
+  void updateManyClouds(const lslam_hector_scan& scan, int nSteps, int nPoints, const float* xyz, const uint8_t* valid,
+                        const uint8_t* take, const float* poseHints, const uint8_t* mapWithoutMatching, const uint8_t* active,
+                        lslam_hector_record* records) {
+    check(lslam_hector_fleet_process_many_clouds(h_, &scan, nSteps, nPoints, xyz, valid, take, poseHints, mapWithoutMatching, active,
+                                                 records));
+  }
+  // clouds in HBM: xyzDev / validDev / takeDev are host arrays of size() device pointers, one block per member (member m's
+  // row of step k is k rows into its block); validDev, takeDev or single entries of them may be nullptr
+  void updateManyCloudsDev(const lslam_hector_scan& scan, int nSteps, int nPoints, const float* const* xyzDev,
+                           const uint8_t* const* validDev, const int32_t* const* takeDev, int takeStride, const float* poseHints,
+                           const uint8_t* mapWithoutMatching, const uint8_t* active, lslam_hector_record* records) {
+    check(lslam_hector_fleet_process_many_clouds_dev(h_, &scan, nSteps, nPoints, xyzDev, validDev, takeDev, takeStride, poseHints,
+                                                     mapWithoutMatching, active, records));
+  }
+  // raw messages in: nodes[size()] are the members' lesson5 nodes (their ImuCallback(s) / OdomCallback(s) before); member m's
+  // ScanCallbacks of the call are its steps with active != 0.  The synchronisation and the de-skew of all members run in 5
+  // launches per call.  records / syncRecords (either may be nullptr): [nSteps * size()].  (Defined below the node.)
+  inline void updateManySynced(LidarUndistortionGpu* const* nodes, const lslam_hector_scan& scan, const lslam_msync_laser& laser,
+                               int nSteps, int nReadings, const float* ranges, int rangesStride, const double* stamps,
+                               const float* timeIncrements, const int64_t* imuSeen, const int64_t* odomSeen, const float* poseHints,
+                               const uint8_t* mapWithoutMatching, const uint8_t* active, lslam_hector_record* records,
+                               lslam_msync_record* syncRecords);
+  // {synced calls, launches of the fleet's synchronisation kernels, buffer growths, host waits}
+  void syncStats(int64_t out[4]) const { lslam_hector_fleet_sync_stats(h_, out); }
   // {steps, member-scans, map updates, calls, host waits, launches of the fleet's kernels}
   void stats(int64_t out[6]) const { lslam_hector_fleet_stats(h_, out); }
   lslam_hector_fleet* handle() { return h_; }
@@ -765,6 +792,19 @@ inline void HectorSlamProcessorGpu::updateManySynced(LidarUndistortionGpu& node,
   check(lslam_hector_process_many_synced(h_, node.syncHandle(), &scan, &laser, nMsgs, nReadings, ranges, rangesStride, stamps,
                                          timeIncrements, imuSeen, odomSeen, poseHints,
                                          mapWithoutMatching ? flags_.data() : nullptr, records, syncRecords));
+}
+
+inline void HectorSlamFleetGpu::updateManySynced(LidarUndistortionGpu* const* nodes, const lslam_hector_scan& scan,
+                                                 const lslam_msync_laser& laser, int nSteps, int nReadings, const float* ranges,
+                                                 int rangesStride, const double* stamps, const float* timeIncrements,
+                                                 const int64_t* imuSeen, const int64_t* odomSeen, const float* poseHints,
+                                                 const uint8_t* mapWithoutMatching, const uint8_t* active,
+                                                 lslam_hector_record* records, lslam_msync_record* syncRecords) {
+  std::vector<lslam_msync*> syncs;
+  for (int r = 0; r < size() && nodes; ++r) syncs.push_back(nodes[r] ? nodes[r]->syncHandle() : nullptr);
+  check(lslam_hector_fleet_process_many_synced(h_, nodes ? syncs.data() : nullptr, &scan, &laser, nSteps, nReadings, ranges,
+                                               rangesStride, stamps, timeIncrements, imuSeen, odomSeen, poseHints,
+                                               mapWithoutMatching, active, records, syncRecords));
 }
 
 // lesson1's LaserScan (lesson1/src/feature_detection.cc): ScanCallback's corner extraction, for one scan or many per

@@ -983,6 +983,66 @@ int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, c
  * fleet's four kernels (copies and the clearing of an exhausted key plane are not launches of them)} */
 int lslam_hector_fleet_stats(const lslam_hector_fleet* f, int64_t out[6]);
 
+/* The fleet's GATED forms: the clouds of lslam_hector_process_many_clouds[_dev] and the raw messages of
+ * lslam_hector_process_many_synced, for R robots per launch.  Entry i = step * R + member is TAKEN iff active[i] != 0 (NULL:
+ * all) and its take word says so (none: `active` alone decides); an entry that is not taken -- masked by the host or refused
+ * on the device -- changes nothing of its member and gives the record that is all zero except n_points = -1.  A member of
+ * which nothing is taken in a call is unchanged: state, cached and resident container, counters, every plane (a resident
+ * container that a longer scan makes grow is moved, not dropped: the single processor's gated forms drop it).  A step is the
+ * chain cloud -> container, match, mark, apply: 4 launches whatever R is; lslam_hector_fleet_stats counts them like the
+ * ungated ones.  One host synchronisation per call.  A member's `scans` / `map_updates` and the fleet's advance by the taken
+ * scans.  Equivalence: after the call member m is bit for bit what lslam_hector_process_many_clouds[_dev] /
+ * lslam_hector_process_many_synced leaves when run on it alone over its active entries in step order; either route may
+ * continue after the other.  Refused before anything is enqueued, with no processor changed: what
+ * lslam_hector_fleet_process_many refuses.
+ *
+ * Host form: xyz[n_steps * R][n_points][3], valid[n_steps * R][n_points] (NULL: every point), take[n_steps * R] (NULL: all).
+ * Rows of entries with active[i] == 0 are not used. */
+int lslam_hector_fleet_process_many_clouds(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                           const float* xyz, const uint8_t* valid, const uint8_t* take, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out);
+/* Clouds in HBM: xyz_dev, valid_dev and take_dev are HOST arrays of R device pointers, one block per member -- R separate
+ * lslam_msync_scans_dev outputs or slices of one block.  Member m's cloud of step k is at xyz_dev[m] + k * n_points * 3, its
+ * valid flags at valid_dev[m] + k * n_points, its take word (taken iff > 0) at take_dev[m] + k * take_stride, take_stride in
+ * int32 words (22 on &records[0].status of lslam_msync_record).  valid_dev or single entries of it may be NULL (every point
+ * valid); take_dev or single entries of it may be NULL (every scan taken).  Pointers of entries with active[i] == 0 are not
+ * read.  Only hints, flags and `active` go up. */
+int lslam_hector_fleet_process_many_clouds_dev(lslam_hector_fleet* f, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                               const float* const* xyz_dev, const uint8_t* const* valid_dev,
+                                               const int32_t* const* take_dev, int take_stride, const float* pose_hints,
+                                               const uint8_t* map_without_matching, const uint8_t* active,
+                                               lslam_hector_record* out);
+/* Raw messages in: syncs[R] are the members' lesson5 nodes (IMU and odometry pushed into each before).  Member m's
+ * callbacks of the call are its steps with active[i] != 0, in step order; ranges row i, stamps[i], time_increments[i],
+ * imu_seen[i], odom_seen[i] (NULL: every message pushed to that member's handle so far) are read for those only.  Entries with
+ * active[i] == 0 give the not-taken out[i] and an all-zero sync_records[i] (may be NULL).  One laser header and one
+ * n_readings for the whole fleet.  The synchronisation runs for all members at once: S = 5 launches per call (queued rows,
+ * walk, windows, ONE k_deskew_batch, blank) whatever R and n_steps are, plus the angle table when the scan geometry is new;
+ * the buffers of the call and a lazily created lslam_deskew are the fleet's, a handle keeps what outlives a call (queues,
+ * state, queued scan, scan_count, the *_seen counters).  A member handle's n_callbacks and corrected / refused counts advance;
+ * its `launches` do not move (lslam_hector_fleet_sync_stats counts them).  After a fleet call lslam_msync_read_windows on a
+ * member handle is LSLAM_ERR_UNSUPPORTED until that handle's next call of its own (the windows live in the fleet's buffer).
+ * Refused before anything is enqueued, with no processor and no lslam_msync handle changed (the *_seen counters included):
+ * LSLAM_ERR_INVALID_ARGUMENT -- NULL handles or arrays (without a device), the same lslam_msync twice or one of another
+ * context, and for any member what lslam_msync_scans_dev refuses (another n_readings than that handle's first scan's, *_seen
+ * that decrease or exceed the pushed count); LSLAM_ERR_UNSUPPORTED -- what lslam_hector_fleet_process_many refuses, more than
+ * 65535 callbacks over all members in one call (k_deskew_batch takes a scan per grid row: make shorter calls), IMU windows
+ * whose summed room exceeds INT_MAX samples.  The processors' side of the call -- pending map updates flushed, every buffer
+ * reserved -- is made ready before the nodes walk a callback, so an allocation failure leaves the nodes where they were too.
+ * NOT atomic: a HIP error once launches are under way (LSLAM_ERR_HIP, e.g. from the clearing of an exhausted key plane
+ * between two steps); the nodes have then walked the call's callbacks, as after such an error in
+ * lslam_hector_process_many_synced.  A handle that was reset (lslam_msync_reset keeps its buffers) may continue with scans of
+ * any length. */
+int lslam_hector_fleet_process_many_synced(lslam_hector_fleet* f, struct lslam_msync* const* syncs, const lslam_hector_scan* scan,
+                                           const struct lslam_msync_laser* laser, int n_steps, int n_readings, const float* ranges,
+                                           int ranges_stride, const double* stamps, const float* time_increments,
+                                           const int64_t* imu_seen, const int64_t* odom_seen, const float* pose_hints,
+                                           const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out,
+                                           struct lslam_msync_record* sync_records);
+/* out = {synced calls, launches of the fleet's synchronisation kernels and its k_deskew_batch (5 per call that has a
+ * callback), growths of the synchronisation's buffers, host waits (one per call)} */
+int lslam_hector_fleet_sync_stats(const lslam_hector_fleet* f, int64_t out[4]);
+
 /* ---------------------------------------------------------------------------------------- */
 /* lesson5 lidar motion de-skew (LidarUndistortion::CorrectLaserScan, lesson5/src/            */
 /* lidar_undistortion.cc:339-447) -- SURVEY 8(f) #4.  Pinned (round 4) against the reference's */
