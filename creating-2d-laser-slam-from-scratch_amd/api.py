@@ -521,6 +521,52 @@ class PlicpMatcher:
                                                           j2.ctypes.data, flags.ctypes.data, x_out.ctypes.data))
         return j1, j2, flags, x_out
 
+    def match_clouds(self, xyz, pair_ref, pair_sens, valid=None, first_guess=None, out=None):
+        """xyz: [n_clouds, n, 3] float32 clouds in the de-skew's layout (Deskewer.batch, MotionSync.scans, IcpMatcher.convert),
+        valid: [n_clouds, n] uint8 or None (every point) -> PLICP_RECORD[n_pairs].  No laser is needed: a point takes part iff
+        its valid byte is set and x, y are finite; its reading index is its position in the cloud."""
+        c = np.ascontiguousarray(xyz, dtype=np.float32)
+        if c.ndim != 3 or c.shape[2] != 3:
+            raise ValueError("xyz must be [n_clouds, n, 3]")
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8).reshape(c.shape[0], c.shape[1])
+        pr = np.ascontiguousarray(pair_ref, dtype=np.int32)
+        ps = np.ascontiguousarray(pair_sens, dtype=np.int32)
+        if pr.shape != ps.shape or pr.ndim != 1:
+            raise ValueError("pair_ref and pair_sens must be two [n_pairs] arrays")
+        g = None if first_guess is None else _f64(first_guess).reshape(len(pr), 3)
+        rec = np.zeros(len(pr), PLICP_RECORD) if out is None else out
+        self.ctx.check(self.L.lslam_plicp_match_clouds(self.h, c.shape[0], c.shape[1], c.ctypes.data,
+                                                       None if v is None else v.ctypes.data, len(pr), pr.ctypes.data, ps.ctypes.data,
+                                                       None if g is None else g.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def match_clouds_dev(self, n_clouds: int, n_points: int, xyz_ptr: int, valid_ptr, pair_ref, pair_sens, first_guess_ptr,
+                         records_ptr: int):
+        """The same with clouds, valid bytes (may be None), first guesses (may be None) and records in HBM: asynchronous on the
+        context's stream, no host wait.  The pair indices are host arrays."""
+        pr = np.ascontiguousarray(pair_ref, dtype=np.int32)
+        ps = np.ascontiguousarray(pair_sens, dtype=np.int32)
+        self.ctx.check(self.L.lslam_plicp_match_clouds_dev(self.h, n_clouds, n_points, xyz_ptr, valid_ptr, len(pr), pr.ctypes.data,
+                                                           ps.ctypes.data, first_guess_ptr, records_ptr))
+
+    def debug_iteration_clouds(self, ref_xyz, sens_xyz, x_in=(0.0, 0.0, 0.0), ref_valid=None, sens_valid=None):
+        """debug_iteration on two [n, 3] clouds (valid bytes or None): j1, j2, flags per point of the sens cloud."""
+        a = np.ascontiguousarray(ref_xyz, dtype=np.float32)
+        b = np.ascontiguousarray(sens_xyz, dtype=np.float32)
+        if a.shape != b.shape or a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("two [n, 3] clouds of one length")
+        n = len(a)
+        rv = None if ref_valid is None else np.ascontiguousarray(ref_valid, dtype=np.uint8).reshape(n)
+        sv = None if sens_valid is None else np.ascontiguousarray(sens_valid, dtype=np.uint8).reshape(n)
+        j1, j2 = np.full(n, -2, np.int32), np.full(n, -2, np.int32)
+        flags = np.zeros(n, np.uint8)
+        x = _f64(x_in)
+        x_out = np.zeros(3)
+        self.ctx.check(self.L.lslam_plicp_debug_iteration_clouds(
+            self.h, a.ctypes.data, b.ctypes.data, None if rv is None else rv.ctypes.data, None if sv is None else sv.ctypes.data, n,
+            x.ctypes.data, j1.ctypes.data, j2.ctypes.data, flags.ctypes.data, x_out.ctypes.data))
+        return j1, j2, flags, x_out
+
     def stats(self) -> dict:
         out = (C.c_int64 * 4)()
         self.ctx.check(self.L.lslam_plicp_stats(self.h, out))
@@ -725,6 +771,53 @@ class PlicpOdometry:
         rec = np.zeros((steps, self.n_tracks), PLICP_ODOM_RECORD)
         self.ctx.check(self.L.lslam_plicp_odom_process_many(self.h, steps, nr, r.ctypes.data, stride, st.ctypes.data,
                                                             None if act is None else act.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def process_many_clouds(self, xyz, stamps, valid=None, take=None, active=None):
+        """xyz: [n_steps, n_tracks, n_points, 3] float32 clouds in the de-skew's layout, stamps [n_steps, n_tracks] seconds, valid
+        [n_steps, n_tracks, n_points] or None = every point, take / active [n_steps, n_tracks] or None = every scan ->
+        PLICP_ODOM_RECORD[n_steps, n_tracks].  An entry is taken iff it is active and its take flag is set; one that is not
+        changes nothing of its track (record: zero with iterations = -1).  No laser is needed.  Between resets a handle runs
+        either range calls or cloud calls, with one n_points."""
+        R = self.n_tracks
+        x = np.ascontiguousarray(xyz, dtype=np.float32)
+        if x.ndim == 3 and R == 1:
+            x = x[:, None]
+        if x.ndim != 4 or x.shape[1] != R or x.shape[3] != 3:
+            raise ValueError("xyz must be [n_steps, n_tracks, n_points, 3]")
+        steps, npts = x.shape[0], x.shape[2]
+        st = _f64(stamps).reshape(steps, R)
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid).astype(bool).astype(np.uint8)).reshape(steps, R, npts)
+        t = None if take is None else np.ascontiguousarray(np.asarray(take).astype(bool).astype(np.uint8)).reshape(steps, R)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8).reshape(steps, R)
+        rec = np.zeros((steps, R), PLICP_ODOM_RECORD)
+        self.ctx.check(self.L.lslam_plicp_odom_process_many_clouds(
+            self.h, steps, npts, x.ctypes.data, None if v is None else v.ctypes.data, None if t is None else t.ctypes.data,
+            st.ctypes.data, None if act is None else act.ctypes.data, rec.ctypes.data))
+        return rec
+
+    def process_many_clouds_dev(self, n_steps: int, n_points: int, xyz_ptrs, valid_ptrs, take_ptrs, take_stride: int, stamps,
+                                active=None):
+        """The same on clouds in HBM.  xyz_ptrs / valid_ptrs / take_ptrs: n_tracks device addresses each, one block per track (R
+        MotionSync.scans_dev outputs, or slices of one block); track m's row of step k is k rows into its block.  valid_ptrs,
+        take_ptrs or single entries of them may be None (every point valid / every scan taken).  take words are int32, taken
+        iff > 0, take_stride words apart: the `status` field of an MSYNC_RECORD array with MSYNC_RECORD.itemsize // 4.  stamps
+        and active are host arrays; only they go up."""
+        R = self.n_tracks
+
+        def table(ptrs):
+            if ptrs is None:
+                return None
+            assert len(ptrs) == R, "one device pointer per track"
+            return (C.c_void_p * R)(*[p or None for p in ptrs])
+
+        x, v, t = table(xyz_ptrs), table(valid_ptrs), table(take_ptrs)
+        st = _f64(stamps).reshape(int(n_steps), R)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8).reshape(int(n_steps), R)
+        rec = np.zeros((int(n_steps), R), PLICP_ODOM_RECORD)
+        self.ctx.check(self.L.lslam_plicp_odom_process_many_clouds_dev(
+            self.h, int(n_steps), int(n_points), x, v, t, int(take_stride), st.ctypes.data,
+            None if act is None else act.ctypes.data, rec.ctypes.data))
         return rec
 
     def state(self) -> np.ndarray:
@@ -987,6 +1080,11 @@ def lib() -> C.CDLL:
     L.lslam_plicp_odom_state.argtypes = [vp, vp]
     L.lslam_plicp_odom_process_many.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
     L.lslam_plicp_odom_stats.argtypes = [vp, vp]
+    L.lslam_plicp_match_clouds.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_plicp_match_clouds_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.lslam_plicp_debug_iteration_clouds.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.lslam_plicp_odom_process_many_clouds.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_plicp_odom_process_many_clouds_dev.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
     L.lslam_icp_params_defaults.argtypes = [C.POINTER(IcpParams)]
     L.lslam_icp_params_defaults.restype = None
     L.lslam_icp_create.argtypes = [vp, C.POINTER(IcpParams), C.POINTER(vp)]

@@ -6,6 +6,8 @@
 // One workgroup per pair, ONE launch per batch, the iterations loop on the device, everything per pair in LDS, all fp64:
 //   1. LaserScanToLDP (:220-261): a reading is valid iff range_min < r < range_max; the valid points of both scans are
 //      compacted in order into LDS (ref: qx, qy, qi; sens: px, py, pi), cos/sin from the handle's table (CreateCache).
+//      The cloud forms load points instead (pl_compact_cloud: valid byte and finite x, y; float32 widened; index = position),
+//      which is how a de-skewed scan is matched; from there on the two forms are one code.
 //   2. per iteration, from x: each lane owns sens points; the nearest valid ref point by an exhaustive search, strict `<` in
 //      ascending index (argmin's lowest index wins); j2 = the valid index neighbour of j1 that is closer (d_lo <= d_hi
 //      prefers the lower one); the point-to-line distance.
@@ -102,6 +104,64 @@ __device__ int pl_compact(PlShared& sh, const float* __restrict__ r, int n, cons
   __syncthreads();
   return count;
 }
+
+// The cloud form of the loader (cloud_to_ldp in tools/plicp_cpu.py): point i takes part iff its valid byte is set (no bytes:
+// every point) and x, y are finite; its coordinates are the float32 x, y widened, z is never read, no range window.  The
+// reading index is i.  Same ballots and wave counts as pl_compact.  x, y of point i at p[stride * i], p[stride * i + 1].
+__device__ int pl_compact_cloud(PlShared& sh, const float* __restrict__ p, int stride, const uint8_t* __restrict__ valid, int n,
+                                double* ox, double* oy, unsigned short* oi) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float vx[kPlTiles], vy[kPlTiles];
+  unsigned long long bal[kPlTiles];
+#pragma unroll
+  for (int t = 0; t < kPlTiles; t++) {
+    const int i = t * kPlThreads + tid;
+    const bool in = i < n;
+    vx[t] = in ? p[(size_t)stride * i] : 0.0f;
+    vy[t] = in ? p[(size_t)stride * i + 1] : 0.0f;
+    const bool flagged = in && (!valid || valid[i] != 0);
+    bal[t] = __ballot(flagged && isfinite(vx[t]) && isfinite(vy[t]));
+    if (lane == 0) sh.wcnt[t * kPlWaves + wv] = __popcll(bal[t]);
+  }
+  __syncthreads();
+  int count = 0, pos[kPlTiles];
+#pragma unroll
+  for (int t = 0; t < kPlTiles; t++)
+#pragma unroll
+    for (int w = 0; w < kPlWaves; w++) {
+      if (w == wv) pos[t] = count;
+      count += sh.wcnt[t * kPlWaves + w];
+    }
+#pragma unroll
+  for (int t = 0; t < kPlTiles; t++) {
+    const int i = t * kPlThreads + tid;
+    if ((bal[t] >> lane) & 1ull) {  // (only points i < n are in the ballot; q <= i < kPlMax)
+      const int q = pos[t] + __popcll(bal[t] & ((1ull << lane) - 1ull));
+      ox[q] = (double)vx[t];
+      oy[q] = (double)vy[t];
+      oi[q] = (unsigned short)i;
+    }
+  }
+  __syncthreads();
+  return count;
+}
+
+// What pl_match loads a scan from: a row of ranges on the handle's beam table, or a cloud.
+struct PlRangesSrc {
+  const float* r;
+  const double *tc, *ts;
+  __device__ __forceinline__ int load(PlShared& sh, int n, const PlParams& P, double* ox, double* oy, unsigned short* oi) const {
+    return pl_compact(sh, r, n, P, tc, ts, ox, oy, oi);
+  }
+};
+struct PlCloudSrc {
+  const float* p;        // x, y of point i at p[stride * i], p[stride * i + 1]
+  int stride;            // 3: an xyz cloud; 2: a kept keyframe
+  const uint8_t* valid;  // NULL: every point
+  __device__ __forceinline__ int load(PlShared& sh, int n, const PlParams&, double* ox, double* oy, unsigned short* oi) const {
+    return pl_compact_cloud(sh, p, stride, valid, n, ox, oy, oi);
+  }
+};
 
 // v[i] <- the block's sum of v[i], the same in every thread and in a fixed order
 template <int N>
@@ -267,16 +327,16 @@ __device__ __forceinline__ void pl_normal(const PlShared& sh, int s, double* nx,
 }
 
 // sm_icp(ref, sens, first guess g) for the whole block; every thread returns the same `out`.  dbg_*: per READING of the sens
-// scan, or all NULL.
-__device__ void pl_match(PlShared& sh, const PlParams& P, int n, const float* __restrict__ r_ref, const float* __restrict__ r_sens,
-                         const double* __restrict__ tc, const double* __restrict__ ts, double gx, double gy, double gth, PlOut& out,
-                         int32_t* dbg_j1, int32_t* dbg_j2, uint8_t* dbg_flags) {
+// scan, or all NULL.  Src: PlRangesSrc or PlCloudSrc -- only the loader differs.
+template <typename Src>
+__device__ void pl_match(PlShared& sh, const PlParams& P, int n, const Src& src_ref, const Src& src_sens, double gx, double gy,
+                         double gth, PlOut& out, int32_t* dbg_j1, int32_t* dbg_j2, uint8_t* dbg_flags) {
   const int tid = threadIdx.x, lane = tid & 63;
   out.x[0] = out.x[1] = out.x[2] = 0.0;
   out.error = __builtin_inf();
   out.valid = out.iterations = out.nvalid = 0;
-  const int nr = pl_compact(sh, r_ref, n, P, tc, ts, sh.qx, sh.qy, sh.qi);
-  const int ns = pl_compact(sh, r_sens, n, P, tc, ts, sh.px, sh.py, sh.pi);
+  const int nr = src_ref.load(sh, n, P, sh.qx, sh.qy, sh.qi);
+  const int ns = src_sens.load(sh, n, P, sh.px, sh.py, sh.pi);
   if (dbg_flags)
     for (int i = tid; i < n; i += kPlThreads) {
       dbg_j1[i] = -1;
@@ -447,8 +507,23 @@ k_plicp_match(PlParams P, int n, int ranges_stride, const float* __restrict__ ra
   const size_t b = blockIdx.x;
   const double gx = guess ? guess[3 * b] : 0.0, gy = guess ? guess[3 * b + 1] : 0.0, gth = guess ? guess[3 * b + 2] : 0.0;
   PlOut o;
-  pl_match(sh, P, n, ranges + (size_t)pair_ref[b] * ranges_stride, ranges + (size_t)pair_sens[b] * ranges_stride, tc, ts, gx, gy,
-           gth, o, nullptr, nullptr, nullptr);
+  pl_match(sh, P, n, PlRangesSrc{ranges + (size_t)pair_ref[b] * ranges_stride, tc, ts},
+           PlRangesSrc{ranges + (size_t)pair_sens[b] * ranges_stride, tc, ts}, gx, gy, gth, o, nullptr, nullptr, nullptr);
+  if (threadIdx.x == 0) pl_store(out + b, o);
+}
+
+// the same on clouds: cloud c at xyz + c * n * 3, its valid bytes (valid may be NULL) at valid + c * n
+__global__ void __launch_bounds__(kPlThreads)
+k_plicp_match_clouds(PlParams P, int n, const float* __restrict__ xyz, const uint8_t* __restrict__ valid,
+                     const int32_t* __restrict__ pair_ref, const int32_t* __restrict__ pair_sens, const double* __restrict__ guess,
+                     lslam_plicp_record* __restrict__ out) {
+  __shared__ PlShared sh;
+  const size_t b = blockIdx.x;
+  const double gx = guess ? guess[3 * b] : 0.0, gy = guess ? guess[3 * b + 1] : 0.0, gth = guess ? guess[3 * b + 2] : 0.0;
+  const size_t cr = (size_t)pair_ref[b], cs = (size_t)pair_sens[b];
+  PlOut o;
+  pl_match(sh, P, n, PlCloudSrc{xyz + cr * n * 3, 3, valid ? valid + cr * n : nullptr},
+           PlCloudSrc{xyz + cs * n * 3, 3, valid ? valid + cs * n : nullptr}, gx, gy, gth, o, nullptr, nullptr, nullptr);
   if (threadIdx.x == 0) pl_store(out + b, o);
 }
 
@@ -460,7 +535,21 @@ k_plicp_debug(PlParams P, int n, const float* __restrict__ ranges, const double*
   __shared__ PlShared sh;
   PlOut o;
   P.max_iter = 1;
-  pl_match(sh, P, n, ranges, ranges + n, tc, ts, x_in[0], x_in[1], x_in[2], o, j1, j2, flags);
+  pl_match(sh, P, n, PlRangesSrc{ranges, tc, ts}, PlRangesSrc{ranges + n, tc, ts}, x_in[0], x_in[1], x_in[2], o, j1, j2, flags);
+  const double xs = threadIdx.x == 0 ? o.x[0] : threadIdx.x == 1 ? o.x[1] : o.x[2];
+  if (threadIdx.x < 3) x_out[threadIdx.x] = o.iterations == 1 ? xs : __builtin_nan("");
+}
+
+// the same on two clouds (xyz: [ref | sens], n x 3 each; valid: [ref | sens] bytes, either may be NULL), per POINT of the sens cloud
+__global__ void __launch_bounds__(kPlThreads)
+k_plicp_debug_clouds(PlParams P, int n, const float* __restrict__ xyz, const uint8_t* __restrict__ ref_valid,
+                     const uint8_t* __restrict__ sens_valid, const double* __restrict__ x_in, int32_t* __restrict__ j1,
+                     int32_t* __restrict__ j2, uint8_t* __restrict__ flags, double* __restrict__ x_out) {
+  __shared__ PlShared sh;
+  PlOut o;
+  P.max_iter = 1;
+  pl_match(sh, P, n, PlCloudSrc{xyz, 3, ref_valid}, PlCloudSrc{xyz + (size_t)n * 3, 3, sens_valid}, x_in[0], x_in[1], x_in[2], o, j1,
+           j2, flags);
   const double xs = threadIdx.x == 0 ? o.x[0] : threadIdx.x == 1 ? o.x[1] : o.x[2];
   if (threadIdx.x < 3) x_out[threadIdx.x] = o.iterations == 1 ? xs : __builtin_nan("");
 }
@@ -527,10 +616,11 @@ struct lslam_plicp {
   bool slot_in_flight[kSlots] = {};
   int next_slot = 0;
   // host form
-  DevBuf<float> d_ranges;
+  DevBuf<float> d_ranges, d_xyz;
+  DevBuf<uint8_t> d_valid;
   DevBuf<double> d_guess;
   DevBuf<lslam_plicp_record> d_rec;
-  unsigned char* h_io = nullptr;  // pinned: ranges and guesses up, records down
+  unsigned char* h_io = nullptr;  // pinned: ranges or clouds and guesses up, records down
   size_t h_io_cap = 0;
   // debug
   DevBuf<unsigned char> d_dbg;
@@ -586,9 +676,25 @@ int pl_check(lslam_plicp* f, const char* who, int n_scans, int n_readings, const
   return LSLAM_OK;
 }
 
-// the pair indices up through the next pinned slot, then ONE launch for the whole batch
-int pl_enqueue(lslam_plicp* f, int n_readings, const float* d_ranges, int ranges_stride, int n_pairs, const int32_t* pair_ref,
-               const int32_t* pair_sens, const double* d_guess, lslam_plicp_record* d_out) {
+int pl_check_clouds(lslam_plicp* f, const char* who, int n_clouds, int n_points, const void* xyz, int n_pairs,
+                    const int32_t* pair_ref, const int32_t* pair_sens, const void* out) {
+  if (!f || n_clouds < 0 || n_points < 0 || n_pairs < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  if (n_pairs == 0) return LSLAM_OK;
+  if (n_points > LSLAM_PLICP_MAX_READINGS)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d points per cloud (got %d)", who, LSLAM_PLICP_MAX_READINGS, n_points);
+  if (!xyz || !pair_ref || !pair_sens || !out)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: xyz, pair_ref, pair_sens and out are required", who);
+  for (int b = 0; b < n_pairs; b++)
+    if (pair_ref[b] < 0 || pair_ref[b] >= n_clouds || pair_sens[b] < 0 || pair_sens[b] >= n_clouds)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: pair %d (%d, %d) is outside the %d clouds", who, b, pair_ref[b], pair_sens[b],
+                       n_clouds);
+  return LSLAM_OK;
+}
+
+// the pair indices up through the next pinned slot, then ONE launch for the whole batch: go(d_pair_ref, d_pair_sens)
+template <typename Launch>
+int pl_enqueue(lslam_plicp* f, int n_pairs, const int32_t* pair_ref, const int32_t* pair_sens, Launch&& go) {
   lslam_context* ctx = f->ctx;
   int rc;
   if ((size_t)n_pairs > f->pair_cap) {  // every slot grows together: none may be in flight
@@ -612,15 +718,30 @@ int pl_enqueue(lslam_plicp* f, int n_readings, const float* d_ranges, int ranges
   memcpy(up, pair_ref, (size_t)n_pairs * sizeof(int32_t));
   memcpy(up + n_pairs, pair_sens, (size_t)n_pairs * sizeof(int32_t));
   LSLAM_HIP(ctx, hipMemcpyAsync(f->d_pairs[q].p, up, 2 * (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  launch(ctx, "plicp_match", k_plicp_match, dim3((unsigned)n_pairs), dim3(kPlThreads), 0, pl_params(f->params, f->laser.range_min, f->laser.range_max),
-         n_readings, ranges_stride, d_ranges, (const int32_t*)f->d_pairs[q].p, (const int32_t*)(f->d_pairs[q].p + n_pairs), d_guess,
-         f->laser.tc(), f->laser.ts(), d_out);
+  go((const int32_t*)f->d_pairs[q].p, (const int32_t*)(f->d_pairs[q].p + n_pairs));
   LSLAM_HIP(ctx, hipGetLastError());
   LSLAM_HIP(ctx, hipEventRecord(f->slot_done[q], ctx->stream));
   f->slot_in_flight[q] = true;
   f->n_launches++;
   f->n_pairs += n_pairs;
   return LSLAM_OK;
+}
+
+int pl_enqueue_ranges(lslam_plicp* f, int n_readings, const float* d_ranges, int ranges_stride, int n_pairs, const int32_t* pair_ref,
+                      const int32_t* pair_sens, const double* d_guess, lslam_plicp_record* d_out) {
+  return pl_enqueue(f, n_pairs, pair_ref, pair_sens, [&](const int32_t* d_ref, const int32_t* d_sens) {
+    launch(f->ctx, "plicp_match", k_plicp_match, dim3((unsigned)n_pairs), dim3(kPlThreads), 0,
+           pl_params(f->params, f->laser.range_min, f->laser.range_max), n_readings, ranges_stride, d_ranges, d_ref, d_sens, d_guess,
+           f->laser.tc(), f->laser.ts(), d_out);
+  });
+}
+
+int pl_enqueue_clouds(lslam_plicp* f, int n_points, const float* d_xyz, const uint8_t* d_valid, int n_pairs, const int32_t* pair_ref,
+                      const int32_t* pair_sens, const double* d_guess, lslam_plicp_record* d_out) {
+  return pl_enqueue(f, n_pairs, pair_ref, pair_sens, [&](const int32_t* d_ref, const int32_t* d_sens) {
+    launch(f->ctx, "plicp_match_clouds", k_plicp_match_clouds, dim3((unsigned)n_pairs), dim3(kPlThreads), 0,
+           pl_params(f->params, 0.0, 0.0), n_points, d_xyz, d_valid, d_ref, d_sens, d_guess, d_out);
+  });
 }
 
 }  // namespace
@@ -676,6 +797,8 @@ void lslam_plicp_destroy(lslam_plicp* f) {
   if (f->h_io) (void)hipHostFree(f->h_io);
   f->laser.d_table.release();
   f->d_ranges.release();
+  f->d_xyz.release();
+  f->d_valid.release();
   f->d_guess.release();
   f->d_rec.release();
   f->d_dbg.release();
@@ -704,7 +827,7 @@ int lslam_plicp_match_batch_dev(lslam_plicp* f, int n_scans, int n_readings, con
                     out_dev);
   if (rc || n_pairs == 0) return rc;
   LSLAM_HIP(f->ctx, hipSetDevice(f->ctx->device));
-  return pl_enqueue(f, n_readings, ranges_dev, ranges_stride, n_pairs, pair_ref, pair_sens, first_guess_dev, out_dev);
+  return pl_enqueue_ranges(f, n_readings, ranges_dev, ranges_stride, n_pairs, pair_ref, pair_sens, first_guess_dev, out_dev);
 }
 
 int lslam_plicp_match_batch(lslam_plicp* f, int n_scans, int n_readings, const float* ranges, int ranges_stride, int n_pairs,
@@ -734,8 +857,8 @@ int lslam_plicp_match_batch(lslam_plicp* f, int n_scans, int n_readings, const f
     memcpy(h_guess, first_guess, guess_bytes);
     LSLAM_HIP(ctx, hipMemcpyAsync(f->d_guess.p, h_guess, guess_bytes, hipMemcpyHostToDevice, ctx->stream));
   }
-  if ((rc = pl_enqueue(f, n_readings, f->d_ranges.p, width, n_pairs, pair_ref, pair_sens, first_guess ? f->d_guess.p : nullptr,
-                       f->d_rec.p)))
+  if ((rc = pl_enqueue_ranges(f, n_readings, f->d_ranges.p, width, n_pairs, pair_ref, pair_sens, first_guess ? f->d_guess.p : nullptr,
+                              f->d_rec.p)))
     return rc;
   LSLAM_HIP(ctx, hipMemcpyAsync(h_rec, f->d_rec.p, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -785,6 +908,101 @@ int lslam_plicp_debug_iteration(lslam_plicp* f, const float* ranges_ref, const f
   return LSLAM_OK;
 }
 
+int lslam_plicp_match_clouds_dev(lslam_plicp* f, int n_clouds, int n_points, const float* xyz_dev, const uint8_t* valid_dev, int n_pairs,
+                                 const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess_dev,
+                                 lslam_plicp_record* out_dev) {
+  int rc = pl_check_clouds(f, "lslam_plicp_match_clouds_dev", n_clouds, n_points, xyz_dev, n_pairs, pair_ref, pair_sens, out_dev);
+  if (rc || n_pairs == 0) return rc;
+  LSLAM_HIP(f->ctx, hipSetDevice(f->ctx->device));
+  return pl_enqueue_clouds(f, n_points, xyz_dev, valid_dev, n_pairs, pair_ref, pair_sens, first_guess_dev, out_dev);
+}
+
+int lslam_plicp_match_clouds(lslam_plicp* f, int n_clouds, int n_points, const float* xyz, const uint8_t* valid, int n_pairs,
+                             const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess, lslam_plicp_record* out) {
+  int rc = pl_check_clouds(f, "lslam_plicp_match_clouds", n_clouds, n_points, xyz, n_pairs, pair_ref, pair_sens, out);
+  if (rc || n_pairs == 0) return rc;
+  lslam_context* ctx = f->ctx;
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t pts = (size_t)n_clouds * n_points;
+  const size_t plane = pts * 3 * sizeof(float), flag_bytes = valid ? pts : 0;
+  const size_t guess_bytes = first_guess ? (size_t)n_pairs * 3 * sizeof(double) : 0;
+  const size_t rec_bytes = (size_t)n_pairs * sizeof(lslam_plicp_record);
+  // pinned: [records | guesses | xyz | valid] (every call ends with a wait: nothing in flight reads this buffer at the next call)
+  if ((rc = pl_pinned(f, &f->h_io, &f->h_io_cap, rec_bytes + guess_bytes + plane + flag_bytes)) ||
+      (rc = pl_reserve(f, f->d_xyz, pts * 3 + 1)) || (rc = pl_reserve(f, f->d_rec, (size_t)n_pairs)) ||
+      (valid && (rc = pl_reserve(f, f->d_valid, pts + 1))) || (first_guess && (rc = pl_reserve(f, f->d_guess, (size_t)n_pairs * 3))))
+    return rc;
+  unsigned char* const h_rec = f->h_io;
+  double* const h_guess = reinterpret_cast<double*>(f->h_io + rec_bytes);
+  unsigned char* const h_xyz = f->h_io + rec_bytes + guess_bytes;
+  unsigned char* const h_valid = h_xyz + plane;
+  if (pts) {
+    memcpy(h_xyz, xyz, plane);
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_xyz.p, h_xyz, plane, hipMemcpyHostToDevice, ctx->stream));
+    if (valid) {
+      memcpy(h_valid, valid, flag_bytes);
+      LSLAM_HIP(ctx, hipMemcpyAsync(f->d_valid.p, h_valid, flag_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+  }
+  if (first_guess) {
+    memcpy(h_guess, first_guess, guess_bytes);
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_guess.p, h_guess, guess_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if ((rc = pl_enqueue_clouds(f, n_points, f->d_xyz.p, valid ? f->d_valid.p : nullptr, n_pairs, pair_ref, pair_sens,
+                              first_guess ? f->d_guess.p : nullptr, f->d_rec.p)))
+    return rc;
+  LSLAM_HIP(ctx, hipMemcpyAsync(h_rec, f->d_rec.p, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  f->n_waits++;
+  for (int q = 0; q < lslam_plicp::kSlots; q++) f->slot_in_flight[q] = false;  // the stream has drained
+  memcpy(out, h_rec, rec_bytes);
+  return LSLAM_OK;
+}
+
+int lslam_plicp_debug_iteration_clouds(lslam_plicp* f, const float* ref_xyz, const float* sens_xyz, const uint8_t* ref_valid,
+                                       const uint8_t* sens_valid, int n, const double x_in[3], int32_t* j1, int32_t* j2,
+                                       uint8_t* flags, double x_out[3]) {
+  if (!f) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = f->ctx;
+  if (!ref_xyz || !sens_xyz || !x_in || !j1 || !j2 || !flags || !x_out || n < 0)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_plicp_debug_iteration_clouds: every pointer but the valid bytes is required");
+  if (n > LSLAM_PLICP_MAX_READINGS)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_plicp_debug_iteration_clouds: at most %d points per cloud (got %d)",
+                     LSLAM_PLICP_MAX_READINGS, n);
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  // device block: [x_in 3 | x_out 3] doubles, [ref | sens] xyz floats, j1, j2 int32, [ref | sens] valid bytes, flags bytes
+  const size_t o_c = 6 * sizeof(double), o_j1 = o_c + 6 * (size_t)n * sizeof(float), o_j2 = o_j1 + (size_t)n * 4;
+  const size_t o_v = o_j2 + (size_t)n * 4, o_f = o_v + 2 * (size_t)n;
+  const size_t bytes = o_f + (size_t)n;
+  int rc;
+  if ((rc = pl_reserve(f, f->d_dbg, bytes)) || (rc = pl_pinned(f, &f->h_io, &f->h_io_cap, bytes))) return rc;
+  memset(f->h_io, 0, bytes);
+  memcpy(f->h_io, x_in, 3 * sizeof(double));
+  if (n) {
+    memcpy(f->h_io + o_c, ref_xyz, 3 * (size_t)n * sizeof(float));
+    memcpy(f->h_io + o_c + 3 * (size_t)n * sizeof(float), sens_xyz, 3 * (size_t)n * sizeof(float));
+    if (ref_valid) memcpy(f->h_io + o_v, ref_valid, (size_t)n);
+    if (sens_valid) memcpy(f->h_io + o_v + n, sens_valid, (size_t)n);
+  }
+  unsigned char* d = f->d_dbg.p;
+  LSLAM_HIP(ctx, hipMemcpyAsync(d, f->h_io, bytes, hipMemcpyHostToDevice, ctx->stream));
+  launch(ctx, "plicp_debug_clouds", k_plicp_debug_clouds, dim3(1), dim3(kPlThreads), 0, pl_params(f->params, 0.0, 0.0), n,
+         (const float*)(d + o_c), (const uint8_t*)(ref_valid ? d + o_v : nullptr), (const uint8_t*)(sens_valid ? d + o_v + n : nullptr),
+         (const double*)d, (int32_t*)(d + o_j1), (int32_t*)(d + o_j2), (uint8_t*)(d + o_f), (double*)(d + 3 * sizeof(double)));
+  LSLAM_HIP(ctx, hipGetLastError());
+  f->n_launches++;
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->h_io, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  f->n_waits++;
+  memcpy(x_out, f->h_io + 3 * sizeof(double), 3 * sizeof(double));
+  if (n) {
+    memcpy(j1, f->h_io + o_j1, (size_t)n * 4);
+    memcpy(j2, f->h_io + o_j2, (size_t)n * 4);
+    memcpy(flags, f->h_io + o_f, (size_t)n);
+  }
+  return LSLAM_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
@@ -814,6 +1032,77 @@ struct PlOdomConsts {
 };
 static_assert(sizeof(lslam_plicp_odom_track) == 80, "lslam_plicp_odom_track is 80 bytes");
 
+struct PlOdomRun {  // a track while its workgroup walks it
+  lslam_plicp_odom_track st;
+  Se2 base, kf, b2l, l2b;
+};
+
+__device__ __forceinline__ PlOdomRun pl_odom_open(const lslam_plicp_odom_track& st, const PlOdomConsts& K) {
+  PlOdomRun R;
+  R.st = st;
+  R.base = Se2{st.base_in_odom[0], st.base_in_odom[1], st.base_in_odom[2]};
+  R.kf = Se2{st.keyframe[0], st.keyframe[1], st.keyframe[2]};
+  R.b2l = Se2{K.b2l[0], K.b2l[1], K.b2l[2]};
+  R.l2b = se2_inv(R.b2l);
+  return R;
+}
+
+__device__ __forceinline__ void pl_odom_close(PlOdomRun& R, lslam_plicp_odom_track* state) {
+  R.st.base_in_odom[0] = R.base.x; R.st.base_in_odom[1] = R.base.y; R.st.base_in_odom[2] = R.base.th;
+  R.st.keyframe[0] = R.kf.x; R.st.keyframe[1] = R.kf.y; R.st.keyframe[2] = R.kf.th;
+  *state = R.st;
+}
+
+// ScanCallback for one scan `cur` of a track whose keyframe scan is `ref`: fills rec (zeroed by the caller) and returns whether
+// `cur` is the keyframe scan from now on.  The node's arithmetic, for either kind of scan.
+template <typename Src>
+__device__ __forceinline__ bool pl_odom_step(PlShared& sh, const PlParams& P, const PlOdomConsts& K, int n, PlOdomRun& R,
+                                             const Src& ref, const Src& cur, double stamp, lslam_plicp_odom_record& rec) {
+  lslam_plicp_odom_track& st = R.st;
+  Se2 &base = R.base, &kf = R.kf;
+  const Se2 &b2l = R.b2l, &l2b = R.l2b;
+  bool fresh;
+  if (!st.initialized) {  // (:196-212)
+    st.initialized = 1;
+    fresh = true;
+    st.last_icp_time = stamp;
+    rec.flags = 3;
+  } else {
+    const double dt = stamp - st.last_icp_time;
+    // GetPrediction (:442-456), literally: linear.y and linear.z are never set, a negative speed predicts nothing
+    const Se2 pred{st.velocity[0] < 1e-6 ? 0.0 : dt * st.velocity[0], 0.0, 0.0};
+    const Se2 pc = se2_mul(pred, se2_mul(base, se2_inv(kf)));                                         // :361
+    const Se2 pcl = se2_mul(se2_mul(se2_mul(se2_mul(l2b, se2_inv(base)), pc), base), b2l);            // :366
+    PlOut o;
+    pl_match(sh, P, n, ref, cur, pcl.x, pcl.y, se2_yaw(pcl.th), o, nullptr, nullptr, nullptr);
+    Se2 corr{0.0, 0.0, 0.0};  // an invalid match: the identity (the reference reads an uninitialised transform)
+    if (o.valid) {            // :399-413
+      corr = se2_mul(se2_mul(b2l, Se2{o.x[0], o.x[1], o.x[2]}), l2b);
+      base = se2_mul(kf, corr);
+      st.velocity[0] = corr.x / dt;
+      st.velocity[1] = se2_yaw(corr.th) / dt;
+    }
+    // NewKeyframeNeeded (:498-517)
+    st.scan_count++;
+    if (fabs(se2_yaw(corr.th)) > K.kf_ang) {
+      fresh = true;
+    } else if (st.scan_count == K.kf_count) {
+      st.scan_count = 0;
+      fresh = true;
+    } else {
+      fresh = corr.x * corr.x + corr.y * corr.y > K.kf_lin_sq;
+    }
+    if (fresh) kf = base;
+    st.last_icp_time = stamp;
+    rec.x[0] = o.x[0]; rec.x[1] = o.x[1]; rec.x[2] = o.x[2];
+    rec.error = o.error;
+    rec.valid = o.valid; rec.iterations = o.iterations; rec.nvalid = o.nvalid;
+    rec.flags = fresh ? 2 : 0;
+  }
+  rec.base_in_odom[0] = base.x; rec.base_in_odom[1] = base.y; rec.base_in_odom[2] = base.th;
+  return fresh;
+}
+
 __global__ void __launch_bounds__(kPlThreads)
 k_plicp_odom(PlParams P, PlOdomConsts K, int n_tracks, int n_steps, int n, int ranges_stride, const float* __restrict__ ranges,
              const double* __restrict__ stamps, const uint8_t* __restrict__ active, const double* __restrict__ tc,
@@ -821,11 +1110,7 @@ k_plicp_odom(PlParams P, PlOdomConsts K, int n_tracks, int n_steps, int n, int r
              lslam_plicp_odom_record* __restrict__ out) {
   __shared__ PlShared sh;
   const int tid = threadIdx.x, track = blockIdx.x;
-  lslam_plicp_odom_track st = state[track];
-  Se2 base{st.base_in_odom[0], st.base_in_odom[1], st.base_in_odom[2]};
-  Se2 kf{st.keyframe[0], st.keyframe[1], st.keyframe[2]};
-  const Se2 b2l{K.b2l[0], K.b2l[1], K.b2l[2]};
-  const Se2 l2b = se2_inv(b2l);
+  PlOdomRun R = pl_odom_open(state[track], K);
   float* const kf_row = kf_scans + (size_t)track * kPlMax;
   const float* ref = kf_row;
   int ref_step = -1;
@@ -840,60 +1125,68 @@ k_plicp_odom(PlParams P, PlOdomConsts K, int n_tracks, int n_steps, int n, int r
       continue;
     }
     const float* cur = ranges + idx * (size_t)ranges_stride;
-    const double stamp = stamps[idx];
-    if (!st.initialized) {  // (:196-212)
-      st.initialized = 1;
+    if (pl_odom_step(sh, P, K, n, R, PlRangesSrc{ref, tc, ts}, PlRangesSrc{cur, tc, ts}, stamps[idx], rec)) {
       ref = cur;
       ref_step = step;
-      st.last_icp_time = stamp;
-      rec.flags = 3;
-    } else {
-      const double dt = stamp - st.last_icp_time;
-      // GetPrediction (:442-456), literally: linear.y and linear.z are never set, a negative speed predicts nothing
-      const Se2 pred{st.velocity[0] < 1e-6 ? 0.0 : dt * st.velocity[0], 0.0, 0.0};
-      const Se2 pc = se2_mul(pred, se2_mul(base, se2_inv(kf)));                                         // :361
-      const Se2 pcl = se2_mul(se2_mul(se2_mul(se2_mul(l2b, se2_inv(base)), pc), base), b2l);            // :366
-      PlOut o;
-      pl_match(sh, P, n, ref, cur, tc, ts, pcl.x, pcl.y, se2_yaw(pcl.th), o, nullptr, nullptr, nullptr);
-      Se2 corr{0.0, 0.0, 0.0};  // an invalid match: the identity (the reference reads an uninitialised transform)
-      if (o.valid) {            // :399-413
-        corr = se2_mul(se2_mul(b2l, Se2{o.x[0], o.x[1], o.x[2]}), l2b);
-        base = se2_mul(kf, corr);
-        st.velocity[0] = corr.x / dt;
-        st.velocity[1] = se2_yaw(corr.th) / dt;
-      }
-      // NewKeyframeNeeded (:498-517)
-      bool fresh;
-      st.scan_count++;
-      if (fabs(se2_yaw(corr.th)) > K.kf_ang) {
-        fresh = true;
-      } else if (st.scan_count == K.kf_count) {
-        st.scan_count = 0;
-        fresh = true;
-      } else {
-        fresh = corr.x * corr.x + corr.y * corr.y > K.kf_lin_sq;
-      }
-      if (fresh) {
-        ref = cur;
-        ref_step = step;
-        kf = base;
-      }
-      st.last_icp_time = stamp;
-      rec.x[0] = o.x[0]; rec.x[1] = o.x[1]; rec.x[2] = o.x[2];
-      rec.error = o.error;
-      rec.valid = o.valid; rec.iterations = o.iterations; rec.nvalid = o.nvalid;
-      rec.flags = fresh ? 2 : 0;
     }
-    rec.base_in_odom[0] = base.x; rec.base_in_odom[1] = base.y; rec.base_in_odom[2] = base.th;
     if (tid == 0) out[idx] = rec;
   }
   if (ref_step >= 0)  // the keyframe scan outlives the call
     for (int i = tid; i < n; i += kPlThreads) kf_row[i] = ref[i];
-  if (tid == 0) {
-    st.base_in_odom[0] = base.x; st.base_in_odom[1] = base.y; st.base_in_odom[2] = base.th;
-    st.keyframe[0] = kf.x; st.keyframe[1] = kf.y; st.keyframe[2] = kf.th;
-    state[track] = st;
+  if (tid == 0) pl_odom_close(R, state + track);
+}
+
+// One track's clouds of a call: step k's cloud at xyz + k * step_rows * n * 3, its valid bytes at valid + k * step_rows * n
+// (NULL: every point), its take word at take + k * take_stride (NULL: every step).  step_rows: 1 for a block per track, the
+// track count for the host form's step-major block.
+struct PlTrackClouds {
+  const float* xyz;
+  const uint8_t* valid;
+  const int32_t* take;
+};
+
+// The node on clouds, gated: entry (step, track) is TAKEN iff active says so (NULL: all) and its take word is > 0 (no words:
+// all).  An entry that is not taken touches nothing: neither the state nor the keyframe, and its stamp and cloud are not
+// read.  The keyframe is kept per track as x, y float32 (kf_xy, two per point) and the valid byte (kf_valid).
+__global__ void __launch_bounds__(kPlThreads)
+k_plicp_odom_clouds(PlParams P, PlOdomConsts K, int n_tracks, int n_steps, int n, const PlTrackClouds* __restrict__ tracks,
+                    int step_rows, int take_stride, const double* __restrict__ stamps, const uint8_t* __restrict__ active,
+                    lslam_plicp_odom_track* __restrict__ state, float* __restrict__ kf_xy, uint8_t* __restrict__ kf_valid,
+                    lslam_plicp_odom_record* __restrict__ out) {
+  __shared__ PlShared sh;
+  const int tid = threadIdx.x, track = blockIdx.x;
+  PlOdomRun R = pl_odom_open(state[track], K);
+  const PlTrackClouds T = tracks[track];
+  float* const kf_row = kf_xy + (size_t)track * kPlMax * 2;
+  uint8_t* const kf_flag = kf_valid + (size_t)track * kPlMax;
+  PlCloudSrc ref{kf_row, 2, kf_flag};
+  int ref_step = -1;
+#pragma unroll 1
+  for (int step = 0; step < n_steps; step++) {
+    const size_t idx = (size_t)step * n_tracks + track;
+    lslam_plicp_odom_record rec;
+    memset(&rec, 0, sizeof rec);
+    const bool taken = (!active || active[idx]) && (!T.take || T.take[(size_t)step * take_stride] > 0);
+    if (!taken) {
+      rec.iterations = -1;
+      if (tid == 0) out[idx] = rec;
+      continue;
+    }
+    const size_t row = (size_t)step * step_rows;
+    const PlCloudSrc cur{T.xyz + row * n * 3, 3, T.valid ? T.valid + row * n : nullptr};
+    if (pl_odom_step(sh, P, K, n, R, ref, cur, stamps[idx], rec)) {
+      ref = cur;
+      ref_step = step;
+    }
+    if (tid == 0) out[idx] = rec;
   }
+  if (ref_step >= 0)  // the keyframe cloud outlives the call
+    for (int i = tid; i < n; i += kPlThreads) {
+      kf_row[2 * i] = ref.p[(size_t)3 * i];
+      kf_row[2 * i + 1] = ref.p[(size_t)3 * i + 1];
+      kf_flag[i] = ref.valid ? ref.valid[i] : (uint8_t)1;
+    }
+  if (tid == 0) pl_odom_close(R, state + track);
 }
 
 }  // namespace
@@ -904,8 +1197,12 @@ struct lslam_plicp_odom {
   PlLaser laser;
   PlOdomConsts consts;
   int n_tracks = 0, n_readings = -1;  // the beam count of the keyframe scans held (-1: none yet)
+  bool clouds = false;                // with n_readings >= 0: the keyframes held are clouds, not range rows
   DevBuf<lslam_plicp_odom_track> d_state;
   DevBuf<float> d_kf, d_ranges;
+  DevBuf<float> d_kf_xy, d_xyz;       // cloud calls: the keyframe clouds' x, y; the host form's clouds
+  DevBuf<uint8_t> d_kf_valid, d_valid;
+  DevBuf<PlTrackClouds> d_tracks;
   DevBuf<double> d_stamps;
   DevBuf<uint8_t> d_active;
   DevBuf<lslam_plicp_odom_record> d_rec;
@@ -921,6 +1218,95 @@ int plo_reserve(lslam_plicp_odom* f, DevBuf<T>& b, size_t n) {
   if (n <= b.cap) return LSLAM_OK;
   LSLAM_HIP(f->ctx, b.reserve(n));
   f->n_growths++;
+  return LSLAM_OK;
+}
+
+// Both cloud forms of the node.  Host form: xyz_h (and valid_h, take_h) are step-major host arrays.  Dev form: xyz_h is NULL
+// and xyz_dev / valid_dev / take_dev are host tables of one device pointer per track.  Every refusal comes before anything is
+// enqueued or reserved.  One launch, one host wait.
+int plo_clouds(lslam_plicp_odom* f, const char* who, int n_steps, int n_points, const float* xyz_h, const uint8_t* valid_h,
+               const uint8_t* take_h, const float* const* xyz_dev, const uint8_t* const* valid_dev, const int32_t* const* take_dev,
+               int take_stride, const double* stamps, const uint8_t* active, lslam_plicp_odom_record* out) {
+  lslam_context* ctx = f->ctx;
+  const bool host = xyz_h != nullptr;
+  const int R = f->n_tracks;
+  if (n_points > LSLAM_PLICP_MAX_READINGS)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: at most %d points per cloud (got %d)", who, LSLAM_PLICP_MAX_READINGS, n_points);
+  if (!stamps || !out || (!host && !xyz_dev))
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: xyz, stamps and out are required", who);
+  if (!host) {
+    for (int m = 0; m < R; m++)
+      if (!xyz_dev[m]) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: track %d has no cloud block", who, m);
+    if (take_dev && take_stride < 1) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: take_stride must be at least 1 word", who);
+  }
+  if (f->n_readings >= 0 && !f->clouds)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: the keyframes held are range rows, this call brings clouds (reset first)", who);
+  if (f->n_readings >= 0 && f->n_readings != n_points)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: the keyframe clouds have %d points, this call %d (reset first)", who, f->n_readings,
+                     n_points);
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t S = (size_t)n_steps * R, pts = S * n_points;
+  const size_t rec_bytes = S * sizeof(lslam_plicp_odom_record), st_bytes = S * sizeof(double);
+  const size_t tab_bytes = (size_t)R * sizeof(PlTrackClouds);
+  const size_t plane = host ? pts * 3 * sizeof(float) : 0, flag_bytes = host && valid_h ? pts : 0;
+  const bool gate = active || (host && take_h);  // the host form's take bytes go up folded into the active bytes
+  // pinned: [records | stamps | track table | xyz | valid | active]
+  const size_t want = rec_bytes + st_bytes + tab_bytes + plane + flag_bytes + S;
+  int rc;
+  if (want > f->h_io_cap) {
+    if (f->h_io) (void)hipHostFree(f->h_io);
+    f->h_io = nullptr;
+    f->h_io_cap = 0;
+    const size_t cap = want + want / 4 + 256;
+    LSLAM_HIP(ctx, hipHostMalloc((void**)&f->h_io, cap, hipHostMallocDefault));
+    f->h_io_cap = cap;
+    f->n_growths++;
+  }
+  if ((rc = plo_reserve(f, f->d_kf_xy, (size_t)R * kPlMax * 2)) || (rc = plo_reserve(f, f->d_kf_valid, (size_t)R * kPlMax)) ||
+      (rc = plo_reserve(f, f->d_tracks, (size_t)R)) || (rc = plo_reserve(f, f->d_stamps, S)) || (rc = plo_reserve(f, f->d_rec, S)) ||
+      (gate && (rc = plo_reserve(f, f->d_active, S))) || (host && (rc = plo_reserve(f, f->d_xyz, pts * 3 + 1))) ||
+      (flag_bytes && (rc = plo_reserve(f, f->d_valid, pts))))
+    return rc;
+  unsigned char* const h_rec = f->h_io;
+  double* const h_st = reinterpret_cast<double*>(f->h_io + rec_bytes);
+  PlTrackClouds* const h_tab = reinterpret_cast<PlTrackClouds*>(f->h_io + rec_bytes + st_bytes);
+  unsigned char* const h_xyz = f->h_io + rec_bytes + st_bytes + tab_bytes;
+  unsigned char* const h_valid = h_xyz + plane;
+  uint8_t* const h_act = h_valid + flag_bytes;
+  for (int m = 0; m < R; m++) {
+    if (host)
+      h_tab[m] = PlTrackClouds{f->d_xyz.p + (size_t)m * n_points * 3, flag_bytes ? f->d_valid.p + (size_t)m * n_points : nullptr, nullptr};
+    else
+      h_tab[m] = PlTrackClouds{xyz_dev[m], valid_dev ? valid_dev[m] : nullptr, take_dev ? take_dev[m] : nullptr};
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_tracks.p, h_tab, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+  memcpy(h_st, stamps, st_bytes);
+  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_stamps.p, h_st, st_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (plane) {
+    memcpy(h_xyz, xyz_h, plane);
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_xyz.p, h_xyz, plane, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (flag_bytes) {
+    memcpy(h_valid, valid_h, flag_bytes);
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_valid.p, h_valid, flag_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (gate) {
+    for (size_t k = 0; k < S; k++) h_act[k] = ((!active || active[k]) && (!(host && take_h) || take_h[k])) ? 1 : 0;
+    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_active.p, h_act, S, hipMemcpyHostToDevice, ctx->stream));
+  }
+  launch(ctx, "plicp_odom_clouds", k_plicp_odom_clouds, dim3((unsigned)R), dim3(kPlThreads), 0, pl_params(f->params, 0.0, 0.0),
+         f->consts, R, n_steps, n_points, (const PlTrackClouds*)f->d_tracks.p, host ? R : 1, host ? 1 : take_stride,
+         (const double*)f->d_stamps.p, (const uint8_t*)(gate ? f->d_active.p : nullptr), f->d_state.p, f->d_kf_xy.p, f->d_kf_valid.p,
+         f->d_rec.p);
+  LSLAM_HIP(ctx, hipGetLastError());
+  f->n_launches++;
+  f->n_readings = n_points;
+  f->clouds = true;
+  LSLAM_HIP(ctx, hipMemcpyAsync(h_rec, f->d_rec.p, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  f->n_waits++;
+  memcpy(out, h_rec, rec_bytes);
+  for (size_t k = 0; k < S; k++) f->n_scans += out[k].iterations != -1 ? 1 : 0;
   return LSLAM_OK;
 }
 
@@ -966,6 +1352,11 @@ void lslam_plicp_odom_destroy(lslam_plicp_odom* f) {
   f->laser.d_table.release();
   f->d_state.release();
   f->d_kf.release();
+  f->d_kf_xy.release();
+  f->d_kf_valid.release();
+  f->d_xyz.release();
+  f->d_valid.release();
+  f->d_tracks.release();
   f->d_ranges.release();
   f->d_stamps.release();
   f->d_active.release();
@@ -1021,6 +1412,8 @@ int lslam_plicp_odom_process_many(lslam_plicp_odom* f, int n_steps, int n_readin
   if (f->n_readings >= 0 && f->n_readings != n_readings)
     return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: the keyframe scans have %d readings, this call %d (reset first)", who, f->n_readings,
                      n_readings);
+  if (f->n_readings >= 0 && f->clouds)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: the keyframes held are clouds, this call brings ranges (reset first)", who);
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
   const size_t S = (size_t)n_steps * f->n_tracks;
   const int width = n_readings > 0 ? n_readings : 1;
@@ -1062,12 +1455,32 @@ int lslam_plicp_odom_process_many(lslam_plicp_odom* f, int n_steps, int n_readin
   LSLAM_HIP(ctx, hipGetLastError());
   f->n_launches++;
   f->n_readings = n_readings;
+  f->clouds = false;
   LSLAM_HIP(ctx, hipMemcpyAsync(h_rec, f->d_rec.p, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   f->n_waits++;
   memcpy(out, h_rec, rec_bytes);
   for (size_t k = 0; k < S; k++) f->n_scans += (!active || active[k]) ? 1 : 0;
   return LSLAM_OK;
+}
+
+int lslam_plicp_odom_process_many_clouds(lslam_plicp_odom* f, int n_steps, int n_points, const float* xyz, const uint8_t* valid,
+                                         const uint8_t* take, const double* stamps, const uint8_t* active,
+                                         lslam_plicp_odom_record* out) {
+  if (!f || n_steps < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  const char* who = "lslam_plicp_odom_process_many_clouds";
+  if (!xyz) return f->ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: xyz, stamps and out are required", who);
+  return plo_clouds(f, who, n_steps, n_points, xyz, valid, take, nullptr, nullptr, nullptr, 1, stamps, active, out);
+}
+
+int lslam_plicp_odom_process_many_clouds_dev(lslam_plicp_odom* f, int n_steps, int n_points, const float* const* xyz_dev,
+                                             const uint8_t* const* valid_dev, const int32_t* const* take_dev, int take_stride,
+                                             const double* stamps, const uint8_t* active, lslam_plicp_odom_record* out) {
+  if (!f || n_steps < 0 || n_points < 0) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (n_steps == 0) return LSLAM_OK;
+  return plo_clouds(f, "lslam_plicp_odom_process_many_clouds_dev", n_steps, n_points, nullptr, nullptr, nullptr, xyz_dev, valid_dev,
+                    take_dev, take_stride, stamps, active, out);
 }
 
 }  // extern "C"

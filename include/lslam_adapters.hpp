@@ -920,6 +920,18 @@ class ScanMatchPLICPGpu {
     for (int k = 0; k < nScans; k++) idx_[k] = k;
     MatchPairs(nScans, nReadings, ranges, rangesStride, nScans - 1, idx_.data(), idx_.data() + 1, nullptr, out);
   }
+  // The same on clouds in the de-skew's layout (xyz: nClouds x nPoints x 3 float32, valid: nClouds x nPoints bytes or NULL):
+  // a point takes part iff its valid byte is set and x, y are finite, its reading index is its position; the constructor's
+  // laser is not read.  This is how a de-skewed scan (lesson5) is matched.
+  void MatchClouds(int nClouds, int nPoints, const float* xyz, const uint8_t* valid, int nPairs, const int32_t* pairRef,
+                   const int32_t* pairSens, const double* firstGuess, lslam_plicp_record* out) {
+    check(lslam_plicp_match_clouds(h_, nClouds, nPoints, xyz, valid, nPairs, pairRef, pairSens, firstGuess, out));
+  }
+  // clouds, valid bytes, first guesses and records in HBM; asynchronous on lslam_stream(), no host wait
+  void MatchCloudsDev(int nClouds, int nPoints, const float* xyzDev, const uint8_t* validDev, int nPairs, const int32_t* pairRef,
+                      const int32_t* pairSens, const double* firstGuessDev, lslam_plicp_record* outDev) {
+    check(lslam_plicp_match_clouds_dev(h_, nClouds, nPoints, xyzDev, validDev, nPairs, pairRef, pairSens, firstGuessDev, outDev));
+  }
   // {pairs matched, kernel launches, buffer growths, host waits}
   void stats(int64_t out[4]) const { lslam_plicp_stats(h_, out); }
   lslam_plicp* handle() { return h_; }
@@ -964,6 +976,20 @@ class PlicpOdometryGpu {
   void ProcessMany(int nSteps, int nReadings, const float* ranges, int rangesStride, const double* stamps,
                    const uint8_t* active, lslam_plicp_odom_record* out) {
     check(lslam_plicp_odom_process_many(h_, nSteps, nReadings, ranges, rangesStride, stamps, active, out));
+  }
+  // The node on clouds (xyz: nSteps x nTracks x nPoints x 3 float32, valid: bytes per point or NULL), gated: an entry is taken
+  // iff active (NULL: all) and take (bytes, NULL: all) say so; one that is not changes nothing of its track (record: zero with
+  // iterations = -1).  Between Reset()s an odometry runs either ProcessMany or ProcessClouds[Dev], with one point count.
+  void ProcessClouds(int nSteps, int nPoints, const float* xyz, const uint8_t* valid, const uint8_t* take, const double* stamps,
+                     const uint8_t* active, lslam_plicp_odom_record* out) {
+    check(lslam_plicp_odom_process_many_clouds(h_, nSteps, nPoints, xyz, valid, take, stamps, active, out));
+  }
+  // The same on clouds in HBM: nTracks device pointers each, one block per track; take words are int32, taken iff > 0,
+  // takeStride words apart (22 on &records[0].status of lslam_msync_record).  stamps, active and out are host arrays.
+  void ProcessCloudsDev(int nSteps, int nPoints, const float* const* xyzDev, const uint8_t* const* validDev,
+                        const int32_t* const* takeDev, int takeStride, const double* stamps, const uint8_t* active,
+                        lslam_plicp_odom_record* out) {
+    check(lslam_plicp_odom_process_many_clouds_dev(h_, nSteps, nPoints, xyzDev, validDev, takeDev, takeStride, stamps, active, out));
   }
   void Reset() { check(lslam_plicp_odom_reset(h_)); }
   // out: nTracks states

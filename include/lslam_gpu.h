@@ -1375,6 +1375,32 @@ int lslam_plicp_match_batch_dev(lslam_plicp* h, int n_scans, int n_readings, con
  * x_out = the solved pose, NaN where the iteration took one of sm_icp's early exits. */
 int lslam_plicp_debug_iteration(lslam_plicp* h, const float* ranges_ref, const float* ranges_sens, int n, const double x_in[3],
                                 int32_t* j1, int32_t* j2, uint8_t* flags, double x_out[3]);
+/* The CLOUD forms: ScanMatchWithPLICP (scan_match_plicp.cc:220-300) on point clouds in the de-skew's layout (what
+ * lslam_deskew_batch, lslam_msync_scans[_dev] and lslam_icp_convert_batch write): xyz = n_clouds x n_points x 3 float32, valid =
+ * n_clouds x n_points bytes or NULL (every point).  A de-skewed scan's points no longer lie on the nominal beam angles, so it has
+ * no ranges form; csm's laser_data carries a theta per reading and sm_icp works on the points alone (cloud_to_ldp in
+ * tools/plicp_cpu.py is the definition).  The rules:
+ *   - point i takes part iff (valid == NULL or valid[i] != 0) and x[i], y[i] are finite;
+ *   - its coordinates are (double)x[i], (double)y[i]: the float32 values widened, no trigonometry; z is ignored, NaN included;
+ *   - no range window is applied and no laser is needed: the producer's valid byte already says what the node's
+ *     range_min < r < range_max (:231) would;
+ *   - the reading index is i: the j1 +- 1 adjacency, "remove doubles" and the (distance, sens order) tie rule go by it exactly as
+ *     in the ranges form, so neighbours are scan-order neighbours even where a de-skewed scan's bearings are not monotone.
+ * Everything else -- the layout of pair_ref / pair_sens (HOST arrays), first_guess, out, the ring of 4 pinned slots, one launch,
+ * the host form waits once and the _dev form (xyz, valid, first_guess, out in HBM) makes no host wait, n_pairs == 0 -- is as
+ * lslam_plicp_match_batch[_dev] above.  A pair's record is byte for byte the same alone and in any batch.
+ * LSLAM_ERR_INVALID_ARGUMENT, outputs untouched: NULL pointers (valid and first_guess may be NULL), a pair index outside
+ * [0, n_clouds).  LSLAM_ERR_UNSUPPORTED: n_points > LSLAM_PLICP_MAX_READINGS. */
+int lslam_plicp_match_clouds(lslam_plicp* h, int n_clouds, int n_points, const float* xyz, const uint8_t* valid, int n_pairs,
+                             const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess, lslam_plicp_record* out);
+int lslam_plicp_match_clouds_dev(lslam_plicp* h, int n_clouds, int n_points, const float* xyz_dev, const uint8_t* valid_dev, int n_pairs,
+                                 const int32_t* pair_ref, const int32_t* pair_sens, const double* first_guess_dev,
+                                 lslam_plicp_record* out_dev);
+/* lslam_plicp_debug_iteration on two clouds of n points (n x 3 float32 each; the valid bytes may be NULL), under the rules
+ * above; j1, j2 and flags are per POINT of the sens cloud.  Host pointers; one launch, one wait. */
+int lslam_plicp_debug_iteration_clouds(lslam_plicp* h, const float* ref_xyz, const float* sens_xyz, const uint8_t* ref_valid,
+                                       const uint8_t* sens_valid, int n, const double x_in[3], int32_t* j1, int32_t* j2,
+                                       uint8_t* flags, double x_out[3]);
 /* out = {pairs matched, kernel launches, buffer growths (device or pinned), host waits} */
 int lslam_plicp_stats(const lslam_plicp* h, int64_t out[4]);
 
@@ -1414,6 +1440,32 @@ int lslam_plicp_odom_state(lslam_plicp_odom* h, lslam_plicp_odom_track* out);
  * call of one handle between resets takes the same n_readings. */
 int lslam_plicp_odom_process_many(lslam_plicp_odom* h, int n_steps, int n_readings, const float* ranges, int ranges_stride,
                                   const double* stamps, const uint8_t* active, lslam_plicp_odom_record* out);
+/* The node of O/ (plicp_odometry.cc) on CLOUDS under the rules of lslam_plicp_match_clouds (scan_match_plicp.cc:220-300 read on
+ * points: valid byte and finite x, y; float32 x, y widened; z ignored; no range window; the reading index is i), with a take
+ * gate, so that lslam_msync_scans_dev output (xyz, valid, records[].status) feeds R tracks with nothing but stamps and flags
+ * crossing the bus.  No laser is needed.  Entry i = step * n_tracks + track.
+ *   Host form: xyz[n_steps * R][n_points][3], valid[n_steps * R][n_points] or NULL, take[n_steps * R] bytes or NULL.
+ *   _dev form: xyz_dev, valid_dev, take_dev are HOST arrays of R device pointers, one block per track: track m's cloud of step k
+ *   is at xyz_dev[m] + k * n_points * 3, its flags at valid_dev[m] + k * n_points, its take word at take_dev[m] + k * take_stride;
+ *   the entry is taken iff the word is > 0.  take_stride counts int32 words: 22 on &records[0].status of lslam_msync_record
+ *   serves as it stands.  valid_dev, take_dev, or single entries of them may be NULL (every point / every step).
+ * stamps, active and out are HOST arrays in both forms; one launch and one host wait per call; in the _dev form only the stamps,
+ * the active bytes and the R-entry pointer table go up.
+ * Entry i is TAKEN iff active[i] != 0 (NULL: all) and its take word says so.  An entry that is not taken changes nothing of its
+ * track -- the state (initialized, scan_count, last_icp_time, velocity), the pose, the keyframe pose and the keyframe cloud stay
+ * as they were; its stamp and its cloud are not read; its record is all zero with iterations = -1.  A track whose first callbacks
+ * are refused is initialised by its first taken scan.  The keyframe is kept per track as a cloud (x, y float32 and the valid byte)
+ * in a buffer of the handle's and outlives the call.  The node's arithmetic -- the prediction, corr_ch, NewKeyframeNeeded and
+ * the three rules above -- is that of the ranges form, unchanged.
+ * Between resets a handle runs EITHER range calls or cloud calls, with one n_points: the other kind, or another length, is
+ * LSLAM_ERR_INVALID_ARGUMENT with nothing enqueued and nothing changed; lslam_plicp_odom_reset frees the choice.
+ * LSLAM_ERR_UNSUPPORTED: n_points > LSLAM_PLICP_MAX_READINGS. */
+int lslam_plicp_odom_process_many_clouds(lslam_plicp_odom* h, int n_steps, int n_points, const float* xyz, const uint8_t* valid,
+                                         const uint8_t* take, const double* stamps, const uint8_t* active,
+                                         lslam_plicp_odom_record* out);
+int lslam_plicp_odom_process_many_clouds_dev(lslam_plicp_odom* h, int n_steps, int n_points, const float* const* xyz_dev,
+                                             const uint8_t* const* valid_dev, const int32_t* const* take_dev, int take_stride,
+                                             const double* stamps, const uint8_t* active, lslam_plicp_odom_record* out);
 /* out = {scans processed, kernel launches, buffer growths, host waits} */
 int lslam_plicp_odom_stats(const lslam_plicp_odom* h, int64_t out[4]);
 

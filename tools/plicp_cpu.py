@@ -65,8 +65,11 @@ class Ldp:
     theta: np.ndarray  # float64 [n]
     min_theta: float
     max_theta: float
+    xy: np.ndarray | None = None  # float64 [n, 2]: the points themselves (cloud_to_ldp); readings / theta are then for information
 
     def points(self) -> np.ndarray:
+        if self.xy is not None:
+            return self.xy
         return np.stack([self.readings * np.cos(self.theta), self.readings * np.sin(self.theta)], axis=1)
 
 
@@ -77,6 +80,27 @@ def laser_scan_to_ldp(ranges, angle_min: float, angle_increment: float, range_mi
         valid = (r > range_min) & (r < range_max)  # :231 (NaN compares false)
     theta = angle_min + np.arange(n, dtype=np.float64) * angle_increment  # :244
     return Ldp(valid.astype(np.int8), np.where(valid, r, -1.0), theta, float(theta[0]), float(theta[-1]))
+
+
+def cloud_to_ldp(xyz, valid=None) -> Ldp:
+    """LaserScanToLDP read on a point cloud (the de-skew's layout: xyz [n, >= 2], valid [n] bytes or None).  csm's laser_data
+    carries a theta per reading and sm_icp works on points() and valid alone, so a cloud whose points have left the nominal
+    beam angles (lesson5's CorrectLaserScan) is matched as it stands:
+      * point i takes part iff (valid is None or valid[i] != 0) and x[i], y[i] are finite;
+      * its coordinates are (double)x[i], (double)y[i] -- the stored values widened, no trigonometry; z is ignored, NaN included;
+      * no range window: the producer's valid byte already says what range_min < r < range_max (:231) would;
+      * the reading index is i: the j1 +- 1 adjacency, "remove doubles" and the (distance, sens order) tie rule go by it.
+    readings / theta are hypot / atan2 of the points, for information; points() returns the points themselves."""
+    p = np.asarray(xyz)
+    xy = np.ascontiguousarray(p[:, :2], dtype=np.float64)  # (a float32 cloud widens exactly)
+    ok = np.isfinite(xy[:, 0]) & np.isfinite(xy[:, 1])
+    if valid is not None:
+        ok &= np.asarray(valid).reshape(len(xy)) != 0
+    xy = np.where(ok[:, None], xy, 0.0)  # (what does not take part is never read; this keeps NaN out of masked arithmetic)
+    r = np.where(ok, np.hypot(xy[:, 0], xy[:, 1]), -1.0)
+    theta = np.arctan2(xy[:, 1], xy[:, 0])
+    n = len(xy)
+    return Ldp(ok.astype(np.int8), r, theta, float(theta[0]) if n else 0.0, float(theta[-1]) if n else 0.0, xy)
 
 
 def _reduce_point_to_line(p: np.ndarray, q: np.ndarray, nrm: np.ndarray):
