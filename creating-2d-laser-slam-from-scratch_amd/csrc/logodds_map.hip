@@ -3470,6 +3470,33 @@ int lslam_map_flush(lslam_map* map) {
 // ------------------------------------------------------------------------------------------
 // lslam_hector_*: the streamed HectorSlamProcessor (device side: k_hs_* above)
 // ------------------------------------------------------------------------------------------
+namespace {
+
+// The input of a call on its way up: ONE pinned staging buffer and the device buffers it feeds (hs_stage_* below), owned once
+// by a processor and once by a fleet.  Every call ends in a wait, so nothing is in flight when the next call reuses or
+// regrows any of them.
+struct HsStage {
+  float* h_in = nullptr;    // pinned: ranges; or points, then counts; or [xyz | take words | valid bytes]
+  size_t h_in_cap = 0;
+  DevBuf<float> d_in;       // ranges; the fleet's points (the single processor's land in its map's d_pts)
+  DevBuf<float> d_xyz;      // clouds: staged from the host, or what the de-skew in front of the processor wrote
+  DevBuf<uint8_t> d_valid;
+  DevBuf<int32_t> d_take;
+  DevBuf<int> d_counts;
+  void release() {
+    if (h_in) (void)hipHostFree(h_in);
+    h_in = nullptr;
+    h_in_cap = 0;
+    d_in.release();
+    d_xyz.release();
+    d_valid.release();
+    d_take.release();
+    d_counts.release();
+  }
+};
+
+}  // namespace
+
 struct lslam_hector {
   lslam_map* map = nullptr;
   float min_dist = 0.4f, min_angle = 0.13f;  // HectorSlamProcessor.h:66-67
@@ -3480,17 +3507,11 @@ struct lslam_hector {
   uint32_t* h_io = nullptr;  // [2][kHsPersistWords]
   lslam_hector_record* h_rec = nullptr;
   size_t h_rec_cap = 0;
-  float* h_ranges = nullptr;  // pinned way up of a call's ranges, or of its points and counts
-  size_t h_ranges_cap = 0;
   DevBuf<lslam_hector_record> d_rec;
-  DevBuf<float> d_ranges;
-  DevBuf<int> d_counts;
-  // de-skewed form: the batched lesson5 stage in front (created with the first such call) and its cloud in HBM
+  HsStage in;
+  // de-skewed form: the batched lesson5 stage in front (created with the first such call); its cloud goes to in.d_xyz
   lslam_deskew* deskew = nullptr;
-  DevBuf<float> d_xyz;
-  DevBuf<uint8_t> d_valid;
-  // gated forms: the host form's take words, and the synced form's lslam_msync_records with their pinned way down
-  DevBuf<int32_t> d_take;
+  // synced form: the walk's lslam_msync_records with their pinned way down
   DevBuf<lslam_msync_record> d_msrec;
   lslam_msync_record* h_msrec = nullptr;
   size_t h_msrec_cap = 0;
@@ -3519,7 +3540,92 @@ int hs_pinned_reserve(lslam_context* ctx, T** p, size_t* cap, size_t want) {
   return LSLAM_OK;
 }
 
-// what both forms refuse before anything touches the device
+// rows x n_readings ranges, `stride` floats apart at the caller's -> s.d_in, packed
+int hs_stage_ranges(lslam_context* ctx, HsStage& s, size_t rows, int n_readings, const float* ranges, size_t stride) {
+  const size_t total = rows * (size_t)n_readings;
+  LSLAM_HIP(ctx, s.d_in.reserve(std::max(total, (size_t)1)));
+  int rc = hs_pinned_reserve(ctx, &s.h_in, &s.h_in_cap, std::max(total, (size_t)1));
+  if (rc || total == 0) return rc;
+  for (size_t i = 0; i < rows; i++) memcpy(s.h_in + i * n_readings, ranges + i * stride, (size_t)n_readings * sizeof(float));
+  LSLAM_HIP(ctx, hipMemcpyAsync(s.d_in.p, s.h_in, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  return LSLAM_OK;
+}
+
+// rows clouds of n_points -> s.d_xyz; their valid bytes (null: none) -> s.d_valid; their take flags (null: none), widened to
+// the int32 words the gated chain reads -> s.d_take
+int hs_stage_clouds(lslam_context* ctx, HsStage& s, size_t rows, int n_points, const float* xyz, const uint8_t* valid,
+                    const uint8_t* take) {
+  const size_t total = rows * (size_t)n_points;
+  const size_t o_take = 3 * total, o_valid = o_take + rows, words = o_valid + (total + 3) / 4;  // pinned: [xyz | take | valid]
+  LSLAM_HIP(ctx, s.d_xyz.reserve(std::max(3 * total, (size_t)1)));
+  if (valid) LSLAM_HIP(ctx, s.d_valid.reserve(std::max(total, (size_t)1)));
+  if (take) LSLAM_HIP(ctx, s.d_take.reserve(rows));
+  int rc = hs_pinned_reserve(ctx, &s.h_in, &s.h_in_cap, words);
+  if (rc) return rc;
+  if (total > 0) {
+    memcpy(s.h_in, xyz, 3 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(s.d_xyz.p, s.h_in, 3 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (valid) {
+      memcpy(s.h_in + o_valid, valid, total);
+      LSLAM_HIP(ctx, hipMemcpyAsync(s.d_valid.p, s.h_in + o_valid, total, hipMemcpyHostToDevice, ctx->stream));
+    }
+  }
+  if (take) {
+    int32_t* t = reinterpret_cast<int32_t*>(s.h_in + o_take);
+    for (size_t i = 0; i < rows; i++) t[i] = take[i] ? 1 : 0;
+    LSLAM_HIP(ctx, hipMemcpyAsync(s.d_take.p, t, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return LSLAM_OK;
+}
+
+// `total` packed points -> d_pts (the caller's: the map's own buffer, or s.d_in), then their rows counts -> s.d_counts.
+// (stage_points' ring waits for a busy slot and drains the stream when it grows; this buffer is never in flight here.)
+int hs_stage_points(lslam_context* ctx, HsStage& s, DevBuf<float>& d_pts, size_t rows, const float* points_xy,
+                    const int32_t* n_points, size_t total) {
+  int rc = hs_pinned_reserve(ctx, &s.h_in, &s.h_in_cap, 2 * total + rows);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, d_pts.reserve(std::max((size_t)2 * total, (size_t)2)));
+  LSLAM_HIP(ctx, s.d_counts.reserve(rows));
+  if (total > 0) {
+    memcpy(s.h_in, points_xy, 2 * total * sizeof(float));
+    LSLAM_HIP(ctx, hipMemcpyAsync(d_pts.p, s.h_in, 2 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  memcpy(s.h_in + 2 * total, n_points, rows * sizeof(int32_t));
+  LSLAM_HIP(ctx, hipMemcpyAsync(s.d_counts.p, s.h_in + 2 * total, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  return LSLAM_OK;
+}
+
+// the de-skew handle in front of a processor or a fleet: made by the first call that needs it
+int hs_ensure_deskew(lslam_context* ctx, lslam_deskew** deskew) { return *deskew ? LSLAM_OK : lslam_deskew_create(ctx, deskew); }
+
+// ---- argument checks that several entry points share
+bool hs_ranges_given(const lslam_hector_scan* scan, int n_readings, const float* ranges, int ranges_stride) {
+  return scan && (n_readings == 0 || (ranges && ranges_stride >= n_readings));
+}
+
+int hs_check_stride(lslam_context* ctx, const char* who, int ranges_stride, int n_readings) {
+  if (ranges_stride < n_readings) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: ranges_stride >= n_readings is required", who);
+  return LSLAM_OK;
+}
+
+// the counts of a container-form call -> their sum and the largest; `active` (null: every scan is) is the fleet's
+int hs_check_counts(lslam_context* ctx, const char* who, size_t rows, const int32_t* n_points, const uint8_t* active,
+                    const float* points_xy, size_t* total, int* cap) {
+  *total = 0;
+  *cap = 0;
+  for (size_t i = 0; i < rows; i++) {
+    if (n_points[i] < 0)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: scan %zu has a negative point count (%d)", who, i, n_points[i]);
+    if (active && !active[i] && n_points[i] != 0)
+      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: scan %zu is not active but has %d points", who, i, n_points[i]);
+    *total += (size_t)n_points[i];
+    *cap = std::max(*cap, n_points[i]);
+  }
+  if (*total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "%s: points_xy is required", who);
+  return LSLAM_OK;
+}
+
+// what every form refuses before anything touches the device
 int hs_check(lslam_hector* h, const char* who, int capacity) {
   lslam_map* map = h->map;
   lslam_context* ctx = map->ctx;
@@ -3537,12 +3643,13 @@ struct HsCall {
   int n_scans = 0, capacity = 0;
   const lslam_hector_scan* scan = nullptr;   // ranges form: project scan k's readings into the map's resident container
   int n_readings = 0;
-  bool cloud = false;                        // de-skewed form: scan k's cloud (h->d_xyz, h->d_valid) goes there instead
-  bool gated = false;                        // cloud forms: scan k's cloud (d_xyz, d_valid; d_valid null: all valid) goes there
-  const float* d_xyz = nullptr;              //   through the gated chain, which takes it iff d_take[k * take_stride] > 0
-  const uint8_t* d_valid = nullptr;          //   (d_take null: every scan)
-  const int32_t* d_take = nullptr;
-  int take_stride = 0;
+  struct {                                   // cloud forms (xyz set): scan k's cloud in HBM goes there instead
+    const float* xyz = nullptr;
+    const uint8_t* valid = nullptr;          //   null: every point is valid
+    const int32_t* take = nullptr;           //   gated chain: scan k is taken iff take[k * take_stride] > 0 (null: every scan)
+    int take_stride = 0;
+  } cloud;
+  bool gated = false;                        // the cloud goes through the gated chain (clouds and synced forms)
   lslam_msync* sync = nullptr;               // synced form: the handle whose walk wrote the take words, and where its
   lslam_msync_record* sync_out = nullptr;    //   records (h->d_msrec) go when they come down with the processor's
   const float* d_points = nullptr;           // container form: the packed points in HBM,
@@ -3552,6 +3659,72 @@ struct HsCall {
   const uint8_t* no_match = nullptr;
   lslam_hector_record* out = nullptr;
 };
+
+// the call of every form that fills the map's resident container from n_scans scans of n_readings readings (or points)
+HsCall hs_scan_call(const lslam_hector_scan* scan, int n_scans, int n_readings, const float* hints, const uint8_t* no_match,
+                    lslam_hector_record* out) {
+  HsCall c;
+  c.n_scans = n_scans;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.hints = hints;
+  c.no_match = no_match;
+  c.out = out;
+  return c;
+}
+
+// the resident container of lslam_map_set_scan, with room for n points
+hipError_t hs_reserve_scan(lslam_map* map, int n) { return map->d_scan.reserve((size_t)2 * std::max(n, 1) + 4); }
+
+// ---- what a processor and the host side of its map hand to a call and take back from it, alone (hs_run) or in a fleet (hf_run)
+
+// state up: the processor's vectors are in its mirror; the cached container's count and origo come from the map (a call of
+// another handle on it, or a host-driven matchData, may have replaced it since)
+void hs_state_up(lslam_hector* h) {
+  const lslam_map* map = h->map;
+  h->mirror.n_cached = map->n_cached;
+  h->mirror.cached_origo[0] = map->cached_origo[0];
+  h->mirror.cached_origo[1] = map->cached_origo[1];
+  h->mirror.updated = 0;
+}
+
+// state down: `words` are the kHsPersistWords that came back; with them, what the host side of the map must know so that
+// every lslam_map_* call goes on working on it.  n_taken: the scans of the call that the processor took.  keep_untaken: a
+// processor that took none stays as it was (a fleet's member: its block came back as it went up, but for `updated`, which is
+// the call's); the single processor always takes its block back.  scan_origo: the origo of the call's projected scans, null
+// in the container form; the resident container of lslam_map_set_scan is the last TAKEN scan's.
+void hs_state_down(lslam_hector* h, const void* words, int n_taken, bool keep_untaken, const float* scan_origo) {
+  if (keep_untaken && n_taken == 0) return;
+  lslam_map* map = h->map;
+  memcpy(&h->mirror, words, kHsPersistWords * 4);
+  if (map->levels.size() > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
+    map->n_cached = h->mirror.n_cached;
+    map->cached_origo[0] = h->mirror.cached_origo[0];
+    map->cached_origo[1] = h->mirror.cached_origo[1];
+  }
+  map->gn_host_n = -1;  // d_cached was rewritten on the device
+  if (scan_origo && n_taken > 0) {
+    map->n_scan = h->mirror.n_live;
+    map->scan_origo[0] = scan_origo[0];
+    map->scan_origo[1] = scan_origo[1];
+  }
+}
+
+// dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:331)
+void hs_scan_origo(const lslam_hector_scan* scan, const ProjectCfg& pc, float origo[2]) {
+  origo[0] = (float)(double)scan->laser_x * pc.scale_to_map;
+  origo[1] = (float)(double)scan->laser_y * pc.scale_to_map;
+}
+
+// one record into its processor's counters -> whether the scan was taken (the gated chain marks the record of one it did not
+// take with n_points = -1, and updated = 0)
+bool hs_count_record(lslam_hector* h, const lslam_hector_record& r) {
+  if (r.n_points < 0) return false;
+  h->n_scans++;
+  h->n_updates += r.updated != 0;
+  return true;
+}
 
 // the cached container must survive a growth of its buffer (levels above 0 of a scan taken without matching read it);
 // *cache_cap: the points either container of a scan of this call may hold
@@ -3612,12 +3785,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     int rc = hs_pinned_reserve(ctx, &h->h_rec, &h->h_rec_cap, (size_t)c.n_scans);
     if (rc) return rc;
   }
-  // ---- state up: the processor's vectors from the mirror, the cached container's count and origo from the map (a
-  // host-driven matchData between two calls may have replaced it)
-  h->mirror.n_cached = map->n_cached;
-  h->mirror.cached_origo[0] = map->cached_origo[0];
-  h->mirror.cached_origo[1] = map->cached_origo[1];
-  h->mirror.updated = 0;
+  hs_state_up(h);
   memcpy(h->h_io, &h->mirror, kHsPersistWords * 4);
   LSLAM_HIP(ctx, hipMemcpyAsync(h->d_state, h->h_io, kHsPersistWords * 4, hipMemcpyHostToDevice, ctx->stream));
   const GnLevels lv = gn_levels_of(map);
@@ -3628,9 +3796,7 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   std::vector<size_t> first;
   if (c.scan) {
     pc = project_cfg(map, c.n_readings, c.scan);
-    // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:331)
-    scan_origo[0] = (float)(double)c.scan->laser_x * pc.scale_to_map;
-    scan_origo[1] = (float)(double)c.scan->laser_y * pc.scale_to_map;
+    hs_scan_origo(c.scan, pc, scan_origo);
   } else {
     first.assign((size_t)c.n_scans + 1, 0);
     for (int k = 0; k < c.n_scans; k++) first[k + 1] = first[k] + (size_t)c.n_points[k];
@@ -3651,25 +3817,23 @@ int hs_run(lslam_hector* h, const HsCall& c) {
     }
     const float* pts;
     const int* n_src;
-    const int32_t* take = c.d_take ? c.d_take + (size_t)k * (size_t)c.take_stride : nullptr;
+    const int32_t* take = c.cloud.take ? c.cloud.take + (size_t)k * (size_t)c.cloud.take_stride : nullptr;
     if (c.scan) {
+      const float* xyz = c.cloud.xyz ? c.cloud.xyz + (size_t)3 * k * c.n_readings : nullptr;
+      const uint8_t* valid = c.cloud.valid ? c.cloud.valid + (size_t)k * c.n_readings : nullptr;
       if (c.gated)
-        launch(ctx, "hg_cloud_container", k_hg_cloud_container, dim3(1), dim3(1024), 0, pc, take,
-               c.d_xyz + (size_t)3 * k * c.n_readings, c.d_valid ? c.d_valid + (size_t)k * c.n_readings : (const uint8_t*)nullptr,
-               map->d_scan.p, d_n_live);
-      else if (c.cloud)
-        launch(ctx, "hs_cloud_container", k_hector_cloud_container, dim3(1), dim3(1024), 0, pc,
-               (const float*)(h->d_xyz.p + (size_t)3 * k * c.n_readings), (const uint8_t*)(h->d_valid.p + (size_t)k * c.n_readings),
-               map->d_scan.p, d_n_live);
+        launch(ctx, "hg_cloud_container", k_hg_cloud_container, dim3(1), dim3(1024), 0, pc, take, xyz, valid, map->d_scan.p, d_n_live);
+      else if (c.cloud.xyz)
+        launch(ctx, "hs_cloud_container", k_hector_cloud_container, dim3(1), dim3(1024), 0, pc, xyz, valid, map->d_scan.p, d_n_live);
       else
-        launch(ctx, "hs_project", k_hector_project, dim3(1), dim3(1024), 0, pc, (const float*)(h->d_ranges.p + (size_t)k * c.n_readings),
+        launch(ctx, "hs_project", k_hector_project, dim3(1), dim3(1024), 0, pc, (const float*)(h->in.d_in.p + (size_t)k * c.n_readings),
                (const double2*)map->d_cossin.p, map->d_scan.p, d_n_live);
       pts = map->d_scan.p;
       n_src = d_n_live;
       sc.origo[0] = scan_origo[0]; sc.origo[1] = scan_origo[1];
     } else {
       pts = c.d_points + 2 * first[k];
-      n_src = h->d_counts.p + k;
+      n_src = h->in.d_counts.p + k;
       sc.origo[0] = c.origos ? c.origos[2 * k] : 0.f;
       sc.origo[1] = c.origos ? c.origos[2 * k + 1] : 0.f;
     }
@@ -3706,28 +3870,12 @@ int hs_run(lslam_hector* h, const HsCall& c) {
   LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   h->n_syncs++;
   h->n_calls++;
-  memcpy(&h->mirror, h->h_io + kHsPersistWords, kHsPersistWords * 4);
-  int n_taken = 0;  // (the gated chain marks the record of a scan it did not take with n_points = -1)
-  for (int k = 0; k < c.n_scans; k++) {
-    n_taken += h->h_rec[k].n_points >= 0;
-    h->n_updates += h->h_rec[k].updated != 0;
-  }
-  h->n_scans += n_taken;
+  int n_taken = 0;
+  for (int k = 0; k < c.n_scans; k++) n_taken += hs_count_record(h, h->h_rec[k]);
   if (c.out) memcpy(c.out, h->h_rec, (size_t)c.n_scans * sizeof(lslam_hector_record));
   if (c.sync_out) memcpy(c.sync_out, h->h_msrec, (size_t)c.n_scans * sizeof(lslam_msync_record));
   if (c.sync) msync_stream_drained(c.sync);
-  // what the host side of the map must know so that every lslam_map_* call goes on working on it
-  if (n_levels > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
-    map->n_cached = h->mirror.n_cached;
-    map->cached_origo[0] = h->mirror.cached_origo[0];
-    map->cached_origo[1] = h->mirror.cached_origo[1];
-  }
-  map->gn_host_n = -1;  // d_cached was rewritten on the device
-  if (c.scan && n_taken > 0) {  // the resident container of lslam_map_set_scan is the last (taken) scan's
-    map->n_scan = h->mirror.n_live;
-    map->scan_origo[0] = scan_origo[0];
-    map->scan_origo[1] = scan_origo[1];
-  }
+  hs_state_down(h, h->h_io + kHsPersistWords, n_taken, false, c.scan ? scan_origo : nullptr);
   return LSLAM_OK;
 }
 
@@ -3762,16 +3910,11 @@ void lslam_hector_destroy(lslam_hector* h) {
   if (h->d_state) (void)hipFree(h->d_state);
   if (h->h_io) (void)hipHostFree(h->h_io);
   if (h->h_rec) (void)hipHostFree(h->h_rec);
-  if (h->h_ranges) (void)hipHostFree(h->h_ranges);
   if (h->h_msrec) (void)hipHostFree(h->h_msrec);
-  h->d_take.release();
   h->d_msrec.release();
   h->d_rec.release();
-  h->d_ranges.release();
-  h->d_counts.release();
   if (h->deskew) lslam_deskew_destroy(h->deskew);
-  h->d_xyz.release();
-  h->d_valid.release();
+  h->in.release();
   delete h;
 }
 
@@ -3802,35 +3945,20 @@ int lslam_hector_process_many(lslam_hector* h, const lslam_hector_scan* scan, in
                               lslam_hector_record* out) {
   if (!h || n_scans < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
   if (n_scans == 0) return LSLAM_OK;
-  if (!scan || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (!hs_ranges_given(scan, n_readings, ranges, ranges_stride)) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_map* map = h->map;
   lslam_context* ctx = map->ctx;
   int rc = hs_check(h, "lslam_hector_process_many", n_readings);
   if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_readings, 1) + 4));
+  LSLAM_HIP(ctx, hs_reserve_scan(map, n_readings));
   bool rebuilt = false;
   rc = ensure_cossin(map, n_readings, scan, &rebuilt);  // (waits for its upload when the scan geometry is new)
   if (rc) return rc;
   h->n_syncs += rebuilt;
-  const size_t total = (size_t)n_scans * (size_t)n_readings;
-  LSLAM_HIP(ctx, h->d_ranges.reserve(std::max(total, (size_t)1)));
-  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, std::max(total, (size_t)1));
+  rc = hs_stage_ranges(ctx, h->in, (size_t)n_scans, n_readings, ranges, (size_t)ranges_stride);
   if (rc) return rc;
-  if (total > 0) {
-    for (int k = 0; k < n_scans; k++)
-      memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  }
-  HsCall c;
-  c.n_scans = n_scans;
-  c.capacity = n_readings;
-  c.scan = scan;
-  c.n_readings = n_readings;
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.out = out;
-  return hs_run(h, c);
+  return hs_run(h, hs_scan_call(scan, n_scans, n_readings, pose_hints, map_without_matching, out));
 }
 
 int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan* scan, int n_scans, int n_readings,
@@ -3840,41 +3968,27 @@ int lslam_hector_process_many_deskewed(lslam_hector* h, const lslam_hector_scan*
                                        const uint8_t* map_without_matching, lslam_hector_record* out) {
   if (!h || n_scans < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
   if (n_scans == 0) return LSLAM_OK;
-  if (!scan || !params || !imu_first || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (!params || !imu_first || !hs_ranges_given(scan, n_readings, ranges, ranges_stride)) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_map* map = h->map;
   lslam_context* ctx = map->ctx;
   int rc = hs_check(h, "lslam_hector_process_many_deskewed", n_readings);
   if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  if (!h->deskew) {
-    rc = lslam_deskew_create(ctx, &h->deskew);
-    if (rc) return rc;
-  }
-  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_readings, 1) + 4));
+  rc = hs_ensure_deskew(ctx, &h->deskew);
+  if (rc) return rc;
+  LSLAM_HIP(ctx, hs_reserve_scan(map, n_readings));
   const size_t total = (size_t)n_scans * (size_t)n_readings;
-  LSLAM_HIP(ctx, h->d_ranges.reserve(std::max(total, (size_t)1)));
-  LSLAM_HIP(ctx, h->d_xyz.reserve(std::max(3 * total, (size_t)1)));
-  LSLAM_HIP(ctx, h->d_valid.reserve(std::max(total, (size_t)1)));
-  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, std::max(total, (size_t)1));
+  LSLAM_HIP(ctx, h->in.d_xyz.reserve(std::max(3 * total, (size_t)1)));
+  LSLAM_HIP(ctx, h->in.d_valid.reserve(std::max(total, (size_t)1)));
+  rc = hs_stage_ranges(ctx, h->in, (size_t)n_scans, n_readings, ranges, (size_t)ranges_stride);
   if (rc) return rc;
-  if (total > 0) {
-    for (int k = 0; k < n_scans; k++)
-      memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  }
   // ONE de-skew launch for the whole call (it does not depend on the map), asynchronous on the same stream
-  rc = lslam_deskew_batch_dev(h->deskew, n_scans, n_readings, h->d_ranges.p, n_readings, params, imu_first, imu_time, imu_rot_x,
-                              imu_rot_y, imu_rot_z, h->d_xyz.p, h->d_valid.p);
+  rc = lslam_deskew_batch_dev(h->deskew, n_scans, n_readings, h->in.d_in.p, n_readings, params, imu_first, imu_time, imu_rot_x,
+                              imu_rot_y, imu_rot_z, h->in.d_xyz.p, h->in.d_valid.p);
   if (rc) return rc;
-  HsCall c;
-  c.n_scans = n_scans;
-  c.capacity = n_readings;
-  c.scan = scan;
-  c.n_readings = n_readings;
-  c.cloud = true;
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.out = out;
+  HsCall c = hs_scan_call(scan, n_scans, n_readings, pose_hints, map_without_matching, out);
+  c.cloud.xyz = h->in.d_xyz.p;
+  c.cloud.valid = h->in.d_valid.p;
   return hs_run(h, c);
 }
 
@@ -3890,20 +4004,10 @@ int lslam_hector_process_many_clouds_dev(lslam_hector* h, const lslam_hector_sca
   int rc = hs_check(h, "lslam_hector_process_many_clouds", n_points);
   if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(n_points, 1) + 4));
-  HsCall c;
-  c.n_scans = n_scans;
-  c.capacity = n_points;
-  c.scan = scan;
-  c.n_readings = n_points;
+  LSLAM_HIP(ctx, hs_reserve_scan(map, n_points));
+  HsCall c = hs_scan_call(scan, n_scans, n_points, pose_hints, map_without_matching, out);
+  c.cloud = {xyz_dev, valid_dev, take_dev, take_stride};
   c.gated = true;
-  c.d_xyz = xyz_dev;
-  c.d_valid = valid_dev;
-  c.d_take = take_dev;
-  c.take_stride = take_stride;
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.out = out;
   return hs_run(h, c);
 }
 
@@ -3917,29 +4021,10 @@ int lslam_hector_process_many_clouds(lslam_hector* h, const lslam_hector_scan* s
   int rc = hs_check(h, "lslam_hector_process_many_clouds", n_points);
   if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  // pinned: [xyz | take words | valid bytes] (the call ends with a wait: the buffer is never in flight here)
-  const size_t total = (size_t)n_scans * (size_t)n_points;
-  const size_t o_take = 3 * total, o_valid = o_take + (size_t)n_scans, words = o_valid + (total + 3) / 4;
-  LSLAM_HIP(ctx, h->d_xyz.reserve(std::max(3 * total, (size_t)1)));
-  if (valid) LSLAM_HIP(ctx, h->d_valid.reserve(std::max(total, (size_t)1)));
-  if (take) LSLAM_HIP(ctx, h->d_take.reserve((size_t)n_scans));
-  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, words);
+  rc = hs_stage_clouds(ctx, h->in, (size_t)n_scans, n_points, xyz, valid, take);
   if (rc) return rc;
-  if (total > 0) {
-    memcpy(h->h_ranges, xyz, 3 * total * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_xyz.p, h->h_ranges, 3 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (valid) {
-      memcpy(h->h_ranges + o_valid, valid, total);
-      LSLAM_HIP(ctx, hipMemcpyAsync(h->d_valid.p, h->h_ranges + o_valid, total, hipMemcpyHostToDevice, ctx->stream));
-    }
-  }
-  if (take) {
-    int32_t* t = reinterpret_cast<int32_t*>(h->h_ranges + o_take);
-    for (int k = 0; k < n_scans; k++) t[k] = take[k] ? 1 : 0;
-    LSLAM_HIP(ctx, hipMemcpyAsync(h->d_take.p, t, (size_t)n_scans * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  }
-  return lslam_hector_process_many_clouds_dev(h, scan, n_scans, n_points, h->d_xyz.p, valid ? h->d_valid.p : (const uint8_t*)nullptr,
-                                              take ? h->d_take.p : (const int32_t*)nullptr, 1, pose_hints, map_without_matching, out);
+  return lslam_hector_process_many_clouds_dev(h, scan, n_scans, n_points, h->in.d_xyz.p, valid ? h->in.d_valid.p : (const uint8_t*)nullptr,
+                                              take ? h->in.d_take.p : (const int32_t*)nullptr, 1, pose_hints, map_without_matching, out);
 }
 
 int lslam_hector_process_many_synced(lslam_hector* h, lslam_msync* sync, const lslam_hector_scan* scan,
@@ -3958,50 +4043,34 @@ int lslam_hector_process_many_synced(lslam_hector* h, lslam_msync* sync, const l
     return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_synced: the lslam_msync handle belongs to another context than the map");
   int rc = hs_check(h, "lslam_hector_process_many_synced", n_readings);
   if (rc) return rc;
-  if (ranges_stride < n_readings)
-    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_synced: ranges_stride >= n_readings is required");
+  rc = hs_check_stride(ctx, "lslam_hector_process_many_synced", ranges_stride, n_readings);
+  if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  if (!h->deskew) {
-    rc = lslam_deskew_create(ctx, &h->deskew);
-    if (rc) return rc;
-  }
+  rc = hs_ensure_deskew(ctx, &h->deskew);
+  if (rc) return rc;
   rc = msync_check_scans(sync, h->deskew, laser, n_msgs, n_readings, stamps, time_increments, imu_seen, odom_seen);
   if (rc) return rc;
   // ---- buffers: ranges up through pinned staging; clouds and the walk's records stay in HBM
   const size_t total = (size_t)n_msgs * (size_t)n_readings;
-  LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * n_readings + 4));
-  LSLAM_HIP(ctx, h->d_ranges.reserve(total));
-  LSLAM_HIP(ctx, h->d_xyz.reserve(3 * total));
-  LSLAM_HIP(ctx, h->d_valid.reserve(total));
+  LSLAM_HIP(ctx, hs_reserve_scan(map, n_readings));
+  LSLAM_HIP(ctx, h->in.d_xyz.reserve(3 * total));
+  LSLAM_HIP(ctx, h->in.d_valid.reserve(total));
   LSLAM_HIP(ctx, h->d_msrec.reserve((size_t)n_msgs));
-  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, total);
-  if (rc) return rc;
   if (sync_records) {
     rc = hs_pinned_reserve(ctx, &h->h_msrec, &h->h_msrec_cap, (size_t)n_msgs);
     if (rc) return rc;
   }
-  for (int k = 0; k < n_msgs; k++)
-    memcpy(h->h_ranges + (size_t)k * n_readings, ranges + (size_t)k * ranges_stride, (size_t)n_readings * sizeof(float));
-  LSLAM_HIP(ctx, hipMemcpyAsync(h->d_ranges.p, h->h_ranges, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  rc = hs_stage_ranges(ctx, h->in, (size_t)n_msgs, n_readings, ranges, (size_t)ranges_stride);
+  if (rc) return rc;
   // the node's callbacks for the whole call: walk, windows, ONE de-skew launch, blank -- asynchronous, no wait
-  rc = lslam_msync_scans_dev(sync, h->deskew, laser, n_msgs, n_readings, h->d_ranges.p, n_readings, stamps, time_increments, imu_seen,
-                             odom_seen, h->d_xyz.p, h->d_valid.p, h->d_msrec.p);
+  rc = lslam_msync_scans_dev(sync, h->deskew, laser, n_msgs, n_readings, h->in.d_in.p, n_readings, stamps, time_increments, imu_seen,
+                             odom_seen, h->in.d_xyz.p, h->in.d_valid.p, h->d_msrec.p);
   if (rc) return rc;
   static_assert(offsetof(lslam_msync_record, status) == 0 && sizeof(lslam_msync_record) % sizeof(int32_t) == 0,
                 "lslam_msync_record::status is the take word of its callback");
-  HsCall c;
-  c.n_scans = n_msgs;
-  c.capacity = n_readings;
-  c.scan = scan;
-  c.n_readings = n_readings;
+  HsCall c = hs_scan_call(scan, n_msgs, n_readings, pose_hints, map_without_matching, out);
+  c.cloud = {h->in.d_xyz.p, h->in.d_valid.p, &h->d_msrec.p->status, (int)(sizeof(lslam_msync_record) / sizeof(int32_t))};
   c.gated = true;
-  c.d_xyz = h->d_xyz.p;
-  c.d_valid = h->d_valid.p;
-  c.d_take = &h->d_msrec.p->status;
-  c.take_stride = (int)(sizeof(lslam_msync_record) / sizeof(int32_t));
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.out = out;
   c.sync = sync;
   c.sync_out = sync_records;
   return hs_run(h, c);
@@ -4015,31 +4084,16 @@ int lslam_hector_process_many_points(lslam_hector* h, int n_scans, const float* 
   if (!n_points) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_map* map = h->map;
   lslam_context* ctx = map->ctx;
+  const char* who = "lslam_hector_process_many_points";
   size_t total = 0;
   int cap = 0;
-  for (int k = 0; k < n_scans; k++) {
-    if (n_points[k] < 0) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_points: scan %d has a negative point count (%d)", k, n_points[k]);
-    total += (size_t)n_points[k];
-    cap = std::max(cap, n_points[k]);
-  }
-  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_process_many_points: points_xy is required");
-  int rc = hs_check(h, "lslam_hector_process_many_points", cap);
+  int rc = hs_check_counts(ctx, who, (size_t)n_scans, n_points, nullptr, points_xy, &total, &cap);
+  if (!rc) rc = hs_check(h, who, cap);
   if (rc) return rc;
-  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_process_many_points: call too large");
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: call too large", who);
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  // points, then counts, through pinned staging of the processor's own (stage_points' ring waits for a busy slot and drains
-  // the stream when it grows; the call's end has synchronised, so this buffer is never in flight here) -> d_pts, d_counts
-  const size_t words = 2 * total + (size_t)n_scans;
-  rc = hs_pinned_reserve(ctx, &h->h_ranges, &h->h_ranges_cap, words);
+  rc = hs_stage_points(ctx, h->in, map->d_pts, (size_t)n_scans, points_xy, n_points, total);
   if (rc) return rc;
-  LSLAM_HIP(ctx, map->d_pts.reserve(std::max((size_t)2 * total, (size_t)2)));
-  LSLAM_HIP(ctx, h->d_counts.reserve((size_t)n_scans));
-  if (total > 0) {
-    memcpy(h->h_ranges, points_xy, 2 * total * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(map->d_pts.p, h->h_ranges, 2 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  }
-  memcpy(h->h_ranges + 2 * total, n_points, (size_t)n_scans * sizeof(int32_t));
-  LSLAM_HIP(ctx, hipMemcpyAsync(h->d_counts.p, h->h_ranges + 2 * total, (size_t)n_scans * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   HsCall c;
   c.n_scans = n_scans;
   c.capacity = cap;
@@ -4082,8 +4136,6 @@ struct lslam_hector_fleet {
   HsState* d_state = nullptr;
   DevBuf<HfScan> d_step;
   DevBuf<lslam_hector_record> d_rec;
-  DevBuf<float> d_in;     // the call's ranges, or its points
-  DevBuf<int> d_counts;
   // pinned staging, the fleet's own
   HfMember* h_mem = nullptr;
   HsState* h_state = nullptr;  // [2][R]: up, down
@@ -4091,11 +4143,7 @@ struct lslam_hector_fleet {
   size_t h_step_cap = 0;
   lslam_hector_record* h_rec = nullptr;
   size_t h_rec_cap = 0;
-  float* h_in = nullptr;  // ranges, or points and then counts, or clouds, take words and valid bytes
-  size_t h_in_cap = 0;
-  // gated cloud form from the host: valid flags and take words (the clouds go through d_in)
-  DevBuf<uint8_t> d_valid;
-  DevBuf<int32_t> d_take;
+  HsStage in;
   // synced form: the fleet's own de-skew handle and fleet-wide synchronisation, made by the first synced call
   lslam_deskew* deskew = nullptr;
   MsyncFleet* msf = nullptr;
@@ -4130,6 +4178,21 @@ struct HfCall {
 
 struct HfWrap { int step, member, level; };  // a key plane whose epochs run out in front of this step
 
+// the call of every form that fills the members' resident containers from n_steps scans each of n_readings readings (or points)
+HfCall hf_scan_call(const lslam_hector_scan* scan, int n_steps, int n_readings, const float* hints, const uint8_t* no_match,
+                    const uint8_t* active, lslam_hector_record* out) {
+  HfCall c;
+  c.n_steps = n_steps;
+  c.capacity = n_readings;
+  c.scan = scan;
+  c.n_readings = n_readings;
+  c.hints = hints;
+  c.no_match = no_match;
+  c.active = active;
+  c.out = out;
+  return c;
+}
+
 // what a call refuses before anything is enqueued
 int hf_check(lslam_hector_fleet* f, const char* who, int capacity) {
   for (lslam_hector* h : f->members) {
@@ -4137,6 +4200,14 @@ int hf_check(lslam_hector_fleet* f, const char* who, int capacity) {
     if (rc) return rc;
   }
   return LSLAM_OK;
+}
+
+// the scans the host offers each member in a call of n_steps (active null: one per step)
+std::vector<int> hf_active_counts(const lslam_hector_fleet* f, int n_steps, const uint8_t* active) {
+  const size_t R = f->members.size(), total = (size_t)n_steps * R;
+  std::vector<int> n_active(R, 0);
+  for (size_t i = 0; i < total; i++) n_active[i % R] += !active || active[i];
+  return n_active;
 }
 
 // Everything of a call that can fail before its first launch: the members' pending updates flushed, and every buffer the call
@@ -4147,8 +4218,7 @@ int hf_reserve(lslam_hector_fleet* f, const HfCall& c, int* ucap, int* max_level
   lslam_context* ctx = f->ctx;
   const int R = (int)f->members.size();
   const size_t total = (size_t)c.n_steps * (size_t)R;
-  std::vector<int> n_active((size_t)R, 0);  // scans the host offers each member in this call
-  for (size_t i = 0; i < total; i++) n_active[i % (size_t)R] += !c.active || c.active[i];
+  const std::vector<int> n_active = hf_active_counts(f, c.n_steps, c.active);
   *ucap = 1;
   *max_levels = 1;
   for (int m = 0; m < R; m++) {
@@ -4157,7 +4227,7 @@ int hf_reserve(lslam_hector_fleet* f, const HfCall& c, int* ucap, int* max_level
     // the device may refuse every one of them, and then the member must be what it was: the points move along.
     if (c.scan && n_active[m]) {
       const float* old = map->d_scan.p;
-      LSLAM_HIP(ctx, map->d_scan.reserve((size_t)2 * std::max(c.n_readings, 1) + 4));
+      LSLAM_HIP(ctx, hs_reserve_scan(map, c.n_readings));
       if (c.gated && old && old != map->d_scan.p && map->n_scan > 0)
         LSLAM_HIP(ctx, hipMemcpyAsync(map->d_scan.p, old, (size_t)2 * map->n_scan * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
@@ -4181,27 +4251,23 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
   const int R = (int)f->members.size();
   const size_t total = (size_t)c.n_steps * (size_t)R;
   const bool ranges_form = c.scan != nullptr;
-  std::vector<int> n_active((size_t)R, 0);  // scans the host offers each member in this call
-  for (size_t i = 0; i < total; i++) n_active[i % (size_t)R] += !c.active || c.active[i];
   int ucap = 1, max_levels = 1;
   {
     int rc = hf_reserve(f, c, &ucap, &max_levels);
     if (rc) return rc;
   }
-  // ---- the member table and the state blocks up: every processor's vectors from its mirror, the cached container's count
-  // and origo from its map (a call of the member's own, or a host-driven matchData, may have replaced it since)
+  // ---- the member table and the state blocks up
+  std::vector<float> scan_origo((size_t)2 * R, 0.f);  // ranges form: the origo of member m's projected scans
   for (int m = 0; m < R; m++) {
     lslam_hector* h = f->members[m];
     lslam_map* map = h->map;
-    h->mirror.n_cached = map->n_cached;
-    h->mirror.cached_origo[0] = map->cached_origo[0];
-    h->mirror.cached_origo[1] = map->cached_origo[1];
-    h->mirror.updated = 0;
+    hs_state_up(h);
     memcpy(&f->h_state[m], &h->mirror, sizeof(HsState));
     HfMember& hm = f->h_mem[m];
     hm.gn = gn_levels_of(map);
     hm.ul = hs_levels_of(map);
     hm.pc = ranges_form ? project_cfg(map, c.n_readings, c.scan) : ProjectCfg{};
+    if (ranges_form) hs_scan_origo(c.scan, hm.pc, &scan_origo[(size_t)2 * m]);
     hm.st = f->d_state + m;
     hm.cached = map->d_cached.p;
     hm.resident = map->d_scan.p;
@@ -4238,9 +4304,8 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
         d.sc.epoch[li] = ++e;
       }
       if (ranges_form) {
-        // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap) (hector_slam.cc:331)
-        d.sc.origo[0] = (float)(double)c.scan->laser_x * f->h_mem[m].pc.scale_to_map;
-        d.sc.origo[1] = (float)(double)c.scan->laser_y * f->h_mem[m].pc.scale_to_map;
+        d.sc.origo[0] = scan_origo[(size_t)2 * m];
+        d.sc.origo[1] = scan_origo[(size_t)2 * m + 1];
         d.pts = map->d_scan.p;
         d.n_src = &(f->d_state + m)->n_live;
         if (c.gated) {
@@ -4248,13 +4313,13 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
           d.valid = c.valid.empty() ? nullptr : c.valid[i];
           d.take = c.take.empty() ? nullptr : c.take[i];
         } else {
-          d.ranges = f->d_in.p + i * (size_t)c.n_readings;
+          d.ranges = f->in.d_in.p + i * (size_t)c.n_readings;
         }
       } else {
         d.sc.origo[0] = c.origos ? c.origos[2 * i] : 0.f;
         d.sc.origo[1] = c.origos ? c.origos[2 * i + 1] : 0.f;
-        d.pts = f->d_in.p + 2 * first[i];
-        d.n_src = f->d_counts.p + i;
+        d.pts = f->in.d_in.p + 2 * first[i];
+        d.n_src = f->in.d_counts.p + i;
       }
       d.rec = f->d_rec.p + i;
     }
@@ -4321,33 +4386,14 @@ int hf_run(lslam_hector_fleet* f, const HfCall& c) {
       r.n_points = -1;
       continue;
     }
-    if (r.n_points < 0) continue;  // refused on the device: hg_skip wrote its record
-    lslam_hector* h = f->members[i % (size_t)R];
+    if (!hs_count_record(f->members[i % (size_t)R], r)) continue;  // refused on the device: hg_skip wrote its record
     n_taken[i % (size_t)R]++;
-    h->n_scans++;
-    h->n_updates += r.updated != 0;
     f->n_scans++;
     f->n_updates += r.updated != 0;
   }
   if (c.out) memcpy(c.out, f->h_rec, total * sizeof(lslam_hector_record));
-  // what each member and the host side of its map must know so that lslam_hector_* and lslam_map_* go on working on them
-  for (int m = 0; m < R; m++) {
-    if (!n_taken[m]) continue;  // (its block came back as it went up, but for `updated`, which is the call's)
-    lslam_hector* h = f->members[m];
-    lslam_map* map = h->map;
-    memcpy(&h->mirror, &f->h_state[R + m], kHsPersistWords * 4);
-    if (map->levels.size() > 1) {  // (as match_data_impl: a single-level map keeps no cached container)
-      map->n_cached = h->mirror.n_cached;
-      map->cached_origo[0] = h->mirror.cached_origo[0];
-      map->cached_origo[1] = h->mirror.cached_origo[1];
-    }
-    map->gn_host_n = -1;  // d_cached was rewritten on the device
-    if (ranges_form) {    // the resident container of lslam_map_set_scan is the member's last scan's
-      map->n_scan = h->mirror.n_live;
-      map->scan_origo[0] = (float)(double)c.scan->laser_x * f->h_mem[m].pc.scale_to_map;
-      map->scan_origo[1] = (float)(double)c.scan->laser_y * f->h_mem[m].pc.scale_to_map;
-    }
-  }
+  for (int m = 0; m < R; m++)
+    hs_state_down(f->members[m], &f->h_state[R + m], n_taken[m], true, ranges_form ? &scan_origo[(size_t)2 * m] : nullptr);
   return LSLAM_OK;
 }
 
@@ -4413,13 +4459,9 @@ void lslam_hector_fleet_destroy(lslam_hector_fleet* f) {
   if (f->h_state) (void)hipHostFree(f->h_state);
   if (f->h_step) (void)hipHostFree(f->h_step);
   if (f->h_rec) (void)hipHostFree(f->h_rec);
-  if (f->h_in) (void)hipHostFree(f->h_in);
   f->d_step.release();
   f->d_rec.release();
-  f->d_in.release();
-  f->d_counts.release();
-  f->d_valid.release();
-  f->d_take.release();
+  f->in.release();
   if (f->deskew) lslam_deskew_destroy(f->deskew);
   msync_fleet_destroy(f->msf);
   delete f;
@@ -4432,36 +4474,21 @@ int lslam_hector_fleet_process_many(lslam_hector_fleet* f, const lslam_hector_sc
                                     const uint8_t* map_without_matching, const uint8_t* active, lslam_hector_record* out) {
   if (!f || n_steps < 0 || n_readings < 0) return LSLAM_ERR_INVALID_ARGUMENT;
   if (n_steps == 0) return LSLAM_OK;
-  if (!scan || (n_readings > 0 && (!ranges || ranges_stride < n_readings))) return LSLAM_ERR_INVALID_ARGUMENT;
+  if (!hs_ranges_given(scan, n_readings, ranges, ranges_stride)) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_context* ctx = f->ctx;
   int rc = hf_check(f, "lslam_hector_fleet_process_many", n_readings);
   if (rc) return rc;
   const size_t rows = (size_t)n_steps * f->members.size();
-  const size_t total = rows * (size_t)n_readings;
-  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many: call too large");
+  if (rows * (size_t)n_readings > (size_t)INT32_MAX / 2)
+    return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many: call too large");
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
   bool rebuilt = false;
   rc = ensure_cossin(f->members[0]->map, n_readings, scan, &rebuilt);  // (waits for its upload when the scan geometry is new)
   if (rc) return rc;
   f->n_syncs += rebuilt;
-  LSLAM_HIP(ctx, f->d_in.reserve(std::max(total, (size_t)1)));
-  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, std::max(total, (size_t)1));
+  rc = hs_stage_ranges(ctx, f->in, rows, n_readings, ranges, (size_t)ranges_stride);
   if (rc) return rc;
-  if (total > 0) {
-    for (size_t i = 0; i < rows; i++)
-      memcpy(f->h_in + i * n_readings, ranges + i * (size_t)ranges_stride, (size_t)n_readings * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  }
-  HfCall c;
-  c.n_steps = n_steps;
-  c.capacity = n_readings;
-  c.scan = scan;
-  c.n_readings = n_readings;
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.active = active;
-  c.out = out;
-  return hf_run(f, c);
+  return hf_run(f, hf_scan_call(scan, n_steps, n_readings, pose_hints, map_without_matching, active, out));
 }
 
 int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, const float* points_xy, const int32_t* n_points,
@@ -4471,33 +4498,17 @@ int lslam_hector_fleet_process_many_points(lslam_hector_fleet* f, int n_steps, c
   if (n_steps == 0) return LSLAM_OK;
   if (!n_points) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_context* ctx = f->ctx;
+  const char* who = "lslam_hector_fleet_process_many_points";
   const size_t rows = (size_t)n_steps * f->members.size();
   size_t total = 0;
   int cap = 0;
-  for (size_t i = 0; i < rows; i++) {
-    if (n_points[i] < 0)
-      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: scan %zu has a negative point count (%d)", i, n_points[i]);
-    if (active && !active[i] && n_points[i] != 0)
-      return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: scan %zu is not active but has %d points", i, n_points[i]);
-    total += (size_t)n_points[i];
-    cap = std::max(cap, n_points[i]);
-  }
-  if (total > 0 && !points_xy) return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_points: points_xy is required");
-  int rc = hf_check(f, "lslam_hector_fleet_process_many_points", cap);
+  int rc = hs_check_counts(ctx, who, rows, n_points, active, points_xy, &total, &cap);
+  if (!rc) rc = hf_check(f, who, cap);
   if (rc) return rc;
-  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_points: call too large");
+  if (total > (size_t)INT32_MAX / 2) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "%s: call too large", who);
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t words = 2 * total + rows;
-  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, words);
+  rc = hs_stage_points(ctx, f->in, f->in.d_in, rows, points_xy, n_points, total);
   if (rc) return rc;
-  LSLAM_HIP(ctx, f->d_in.reserve(std::max((size_t)2 * total, (size_t)2)));
-  LSLAM_HIP(ctx, f->d_counts.reserve(rows));
-  if (total > 0) {
-    memcpy(f->h_in, points_xy, 2 * total * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, 2 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  }
-  memcpy(f->h_in + 2 * total, n_points, rows * sizeof(int32_t));
-  LSLAM_HIP(ctx, hipMemcpyAsync(f->d_counts.p, f->h_in + 2 * total, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   HfCall c;
   c.n_steps = n_steps;
   c.capacity = cap;
@@ -4520,20 +4531,16 @@ int lslam_hector_fleet_process_many_clouds_dev(lslam_hector_fleet* f, const lsla
   if (!scan || (n_points > 0 && !xyz_dev) || (take_dev && take_stride < 1)) return LSLAM_ERR_INVALID_ARGUMENT;
   lslam_context* ctx = f->ctx;
   const size_t R = f->members.size(), total = (size_t)n_steps * R;
-  std::vector<size_t> n_active(R, 0);
-  for (size_t i = 0; i < total; i++) n_active[i % R] += !active || active[i];
-  if (n_points > 0)
+  if (n_points > 0) {
+    const std::vector<int> n_active = hf_active_counts(f, n_steps, active);
     for (size_t m = 0; m < R; m++)
       if (n_active[m] && !xyz_dev[m])
         return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_clouds_dev: member %zu has scans but no cloud block", m);
+  }
   int rc = hf_check(f, "lslam_hector_fleet_process_many_clouds", n_points);
   if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  HfCall c;
-  c.n_steps = n_steps;
-  c.capacity = n_points;
-  c.scan = scan;
-  c.n_readings = n_points;
+  HfCall c = hf_scan_call(scan, n_steps, n_points, pose_hints, map_without_matching, active, out);
   c.gated = true;
   c.xyz.assign(total, nullptr);
   if (valid_dev) c.valid.assign(total, nullptr);
@@ -4545,10 +4552,6 @@ int lslam_hector_fleet_process_many_clouds_dev(lslam_hector_fleet* f, const lsla
     if (valid_dev && valid_dev[m]) c.valid[i] = valid_dev[m] + k * (size_t)n_points;
     if (take_dev && take_dev[m]) c.take[i] = take_dev[m] + k * (size_t)take_stride;
   }
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.active = active;
-  c.out = out;
   return hf_run(f, c);
 }
 
@@ -4564,44 +4567,18 @@ int lslam_hector_fleet_process_many_clouds(lslam_hector_fleet* f, const lslam_he
   const size_t R = f->members.size(), rows = (size_t)n_steps * R, total = rows * (size_t)n_points;
   if (total > (size_t)INT32_MAX / 4) return ctx->fail(LSLAM_ERR_UNSUPPORTED, "lslam_hector_fleet_process_many_clouds: call too large");
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  // pinned: [xyz | take words | valid bytes] (the call ends with a wait: the buffer is never in flight here)
-  const size_t o_take = 3 * total, o_valid = o_take + rows, words = o_valid + (total + 3) / 4;
-  LSLAM_HIP(ctx, f->d_in.reserve(std::max(3 * total, (size_t)1)));
-  if (valid) LSLAM_HIP(ctx, f->d_valid.reserve(std::max(total, (size_t)1)));
-  if (take) LSLAM_HIP(ctx, f->d_take.reserve(rows));
-  rc = hs_pinned_reserve(ctx, &f->h_in, &f->h_in_cap, words);
+  rc = hs_stage_clouds(ctx, f->in, rows, n_points, xyz, valid, take);
   if (rc) return rc;
-  if (total > 0) {
-    memcpy(f->h_in, xyz, 3 * total * sizeof(float));
-    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_in.p, f->h_in, 3 * total * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (valid) {
-      memcpy(f->h_in + o_valid, valid, total);
-      LSLAM_HIP(ctx, hipMemcpyAsync(f->d_valid.p, f->h_in + o_valid, total, hipMemcpyHostToDevice, ctx->stream));
-    }
-  }
-  if (take) {
-    int32_t* t = reinterpret_cast<int32_t*>(f->h_in + o_take);
-    for (size_t i = 0; i < rows; i++) t[i] = take[i] ? 1 : 0;
-    LSLAM_HIP(ctx, hipMemcpyAsync(f->d_take.p, t, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  }
-  HfCall c;
-  c.n_steps = n_steps;
-  c.capacity = n_points;
-  c.scan = scan;
-  c.n_readings = n_points;
+  HfCall c = hf_scan_call(scan, n_steps, n_points, pose_hints, map_without_matching, active, out);
   c.gated = true;
   c.xyz.assign(rows, nullptr);
   if (valid) c.valid.assign(rows, nullptr);
   if (take) c.take.assign(rows, nullptr);
   for (size_t i = 0; i < rows; i++) {
-    c.xyz[i] = f->d_in.p + 3 * i * (size_t)n_points;
-    if (valid) c.valid[i] = f->d_valid.p + i * (size_t)n_points;
-    if (take) c.take[i] = f->d_take.p + i;
+    c.xyz[i] = f->in.d_xyz.p + 3 * i * (size_t)n_points;
+    if (valid) c.valid[i] = f->in.d_valid.p + i * (size_t)n_points;
+    if (take) c.take[i] = f->in.d_take.p + i;
   }
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.active = active;
-  c.out = out;
   return hf_run(f, c);
 }
 
@@ -4630,23 +4607,16 @@ int lslam_hector_fleet_process_many_synced(lslam_hector_fleet* f, lslam_msync* c
   }
   int rc = hf_check(f, "lslam_hector_fleet_process_many_synced", n_readings);
   if (rc) return rc;
-  if (ranges_stride < n_readings)
-    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_hector_fleet_process_many_synced: ranges_stride >= n_readings is required");
+  rc = hs_check_stride(ctx, "lslam_hector_fleet_process_many_synced", ranges_stride, n_readings);
+  if (rc) return rc;
   LSLAM_HIP(ctx, hipSetDevice(ctx->device));
-  if (!f->deskew) {
-    rc = lslam_deskew_create(ctx, &f->deskew);
-    if (rc) return rc;
-  }
+  rc = hs_ensure_deskew(ctx, &f->deskew);
+  if (rc) return rc;
   if (!f->msf) f->msf = msync_fleet_create(ctx);
   rc = msync_fleet_plan(f->msf, syncs, R, f->deskew, laser, n_steps, n_readings, stamps, time_increments, imu_seen, odom_seen, active);
   if (rc) return rc;
-  HfCall c;
-  c.n_steps = n_steps;
-  c.capacity = n_readings;
-  c.scan = scan;
-  c.n_readings = n_readings;
+  HfCall c = hf_scan_call(scan, n_steps, n_readings, pose_hints, map_without_matching, active, out);
   c.gated = true;
-  c.active = active;
   {  // the processors' side of the call is ready before any node walks a callback
     int ucap = 1, max_levels = 1;
     rc = hf_reserve(f, c, &ucap, &max_levels);
@@ -4671,10 +4641,6 @@ int lslam_hector_fleet_process_many_synced(lslam_hector_fleet* f, lslam_msync* c
     c.valid[i] = d_valid + row * (size_t)n_readings;
     c.take[i] = &d_recs[row].status;
   }
-  c.hints = pose_hints;
-  c.no_match = map_without_matching;
-  c.active = active;
-  c.out = out;
   c.msf = f->msf;
   c.sync_out = sync_records;
   return hf_run(f, c);
