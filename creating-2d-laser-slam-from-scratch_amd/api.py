@@ -1029,6 +1029,20 @@ def lib() -> C.CDLL:
     L.lslam_hector_fleet_process_many_synced.argtypes = [vp, vp, C.POINTER(HectorScan), C.POINTER(MsyncLaser), i32, i32, vp, i32,
                                                          vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lslam_hector_fleet_sync_stats.argtypes = [vp, vp]
+    L.lslam_map_write_logodds.argtypes = [vp, i32, vp]
+    L.lslam_map_write_logodds_dev.argtypes = [vp, i32, vp]
+    L.lslam_hector_loc_create.argtypes = [vp, i32, C.POINTER(vp)]
+    L.lslam_hector_loc_destroy.argtypes = [vp]
+    L.lslam_hector_loc_destroy.restype = None
+    L.lslam_hector_loc_size.argtypes = [vp]
+    L.lslam_hector_loc_set_poses.argtypes = [vp, i32, i32, vp]
+    L.lslam_hector_loc_state.argtypes = [vp, i32, vp, vp]
+    L.lslam_hector_loc_set_option.argtypes = [vp, i32, i32]
+    L.lslam_hector_loc_process_many.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, i32, vp, vp, vp]
+    L.lslam_hector_loc_process_many_points.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.lslam_hector_loc_process_many_clouds.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, vp, vp, vp]
+    L.lslam_hector_loc_process_many_clouds_dev.argtypes = [vp, C.POINTER(HectorScan), i32, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.lslam_hector_loc_stats.argtypes = [vp, vp]
     L.lslam_pool_create.argtypes = [i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_create_on.argtypes = [vp, i32, C.POINTER(MatcherConfig), C.POINTER(LaserParams), C.POINTER(vp)]
     L.lslam_pool_destroy.argtypes = [vp]
@@ -1984,6 +1998,8 @@ class OccGridMap:
         h = C.c_void_p()
         ctx.check(self.L.lslam_map_create(ctx.h, size_x, size_y, cell_length, offset[0], offset[1], levels, C.byref(h)))
         self.h = h
+        # what save() records and load() compares: the arguments as the library took them (floats are C floats there)
+        self.geometry = np.array([size_x, size_y, np.float32(cell_length), np.float32(offset[0]), np.float32(offset[1])], np.float64)
         ctx._adopt(self)
 
     def close(self):
@@ -2275,6 +2291,40 @@ class OccGridMap:
 
     def cells_dev_ptr(self, level: int = 0) -> int:
         return self.L.lslam_map_cells_dev_ptr(self.h, level)
+
+    def write_logodds(self, level: int, plane):
+        """The inverse of logodds(): `plane` [size_y, size_x] float32 becomes the level's log-odds plane, bit for bit (NaN,
+        +-inf and -0.0 included).  Containers, update factors and counters stay; the next update treats every cell as not yet
+        touched by its scan."""
+        sx, sy = self.size(level)
+        p = np.ascontiguousarray(plane, dtype=np.float32)
+        if p.size != sx * sy:
+            raise ValueError(f"level {level} takes {sy} x {sx} cells, got {p.shape}")
+        self.ctx.check(self.L.lslam_map_write_logodds(self.h, level, p.ctypes.data))
+
+    def write_logodds_dev(self, level: int, ptr: int):
+        """The same from a float32 plane in HBM (asynchronous on the context's stream); another map's cells_dev_ptr(level) of
+        the same context and level size makes this the device-to-device snapshot."""
+        self.ctx.check(self.L.lslam_map_write_logodds_dev(self.h, level, ptr))
+
+    def save(self, path):
+        """The pyramid as a numpy .npz: geometry (size_x, size_y, cell_length, offset_x, offset_y), levels, level_0 .. level_{n-1}."""
+        planes = {f"level_{i}": self.logodds(i) for i in range(self.levels)}
+        with open(path, "wb") as f:  # (np.savez would append .npz to a bare name)
+            np.savez(f, geometry=self.geometry, levels=np.int32(self.levels), **planes)
+
+    def load(self, path):
+        """Planes saved by save() into this map.  Refuses a file whose geometry or number of levels differs from the map's."""
+        with np.load(path) as z:
+            if not np.array_equal(z["geometry"], self.geometry) or int(z["levels"]) != self.levels:
+                raise ValueError(f"{path}: geometry {z['geometry'].tolist()} x {int(z['levels'])} levels is not this map's "
+                                 f"{self.geometry.tolist()} x {self.levels}")
+            planes = [z[f"level_{i}"] for i in range(self.levels)]
+        for i, p in enumerate(planes):
+            if p.shape != self.size(i)[::-1]:
+                raise ValueError(f"{path}: level {i} is {p.shape}")
+        for i, p in enumerate(planes):
+            self.write_logodds(i, p)
 
 
 HECTOR_RECORD = np.dtype([("pose", np.float32, 3), ("cov", np.float32, (3, 3)), ("updated", np.int32), ("n_points", np.int32),
@@ -2610,6 +2660,134 @@ class HectorFleet:
         out = (C.c_int64 * 6)()
         self.ctx.check(self.L.lslam_hector_fleet_stats(self.h, out))
         return dict(zip(("steps", "scans", "map_updates", "calls", "host_syncs", "launches"), (int(v) for v in out)))
+
+
+class HectorLocaliser:
+    """R trackers localising on ONE finished map (lslam_hector_loc_*): each entry is HectorSlamProcessor::update with the gate
+    never firing -- matchData from the hint or the tracker's own last pose, no map update.  Borrows `map` (an OccGridMap),
+    which it only reads and which stays usable, and changeable, through its own methods between calls.  Per-entry arrays are
+    [n_steps, R, ...] as in HectorFleet; an entry that is not taken leaves its tracker alone (record: zero, n_points = -1)."""
+
+    def __init__(self, map: "OccGridMap", n_trackers: int):
+        self.map, self.ctx, self.L = map, map.ctx, map.L
+        h = C.c_void_p()
+        self.ctx.check(self.L.lslam_hector_loc_create(map.h, int(n_trackers), C.byref(h)))
+        self.h = h
+        self.n_trackers = int(n_trackers)
+        if not hasattr(map, "_processors"):
+            map._processors = []
+        map._processors.append(self)  # closed with the map, before it
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lslam_hector_loc_destroy(self.h)
+            self.h = None
+            if self in getattr(self.map, "_processors", ()):
+                self.map._processors.remove(self)
+
+    def __del__(self):
+        try:
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self) -> int:
+        return int(self.L.lslam_hector_loc_size(self.h))
+
+    def set_poses(self, poses_xyh, first: int = 0):
+        """lastScanMatchPose of trackers first .. first + len(poses) - 1."""
+        p = np.ascontiguousarray(poses_xyh, dtype=np.float32).reshape(-1, 3)
+        self.ctx.check(self.L.lslam_hector_loc_set_poses(self.h, int(first), p.shape[0], p.ctypes.data))
+
+    def state(self, tracker: int):
+        """-> (lastScanMatchPose[3], lastScanMatchCov[3,3]) of one tracker"""
+        pose, cov = np.zeros(3, np.float32), np.zeros(9, np.float32)
+        self.ctx.check(self.L.lslam_hector_loc_state(self.h, int(tracker), pose.ctypes.data, cov.ctypes.data))
+        return pose, cov.reshape(3, 3)
+
+    def set_option(self, name: str, value: int):
+        """'max_steps_per_launch': steps per chunk of a call (0: the default, from the 64 MiB container budget)."""
+        self.ctx.check(self.L.lslam_hector_loc_set_option(self.h, {"max_steps_per_launch": 1}[name], int(value)))
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 6)()
+        self.ctx.check(self.L.lslam_hector_loc_stats(self.h, out))
+        return dict(zip(("steps", "scans", "calls", "host_syncs", "launches", "track_launches"), (int(v) for v in out)))
+
+    def _per_entry(self, n_steps, pose_hints, active):
+        R = self.n_trackers
+        hints = None if pose_hints is None else np.ascontiguousarray(pose_hints, dtype=np.float32).reshape(n_steps * R, 3)
+        act = None if active is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(active, dtype=np.uint8), (n_steps, R))).reshape(n_steps * R)
+        return hints, act
+
+    def process_many(self, ranges, scan: HectorScan, pose_hints=None, active=None) -> np.ndarray:
+        """ranges: [n_steps, R, n_readings] float32 LaserScans of one geometry -> HECTOR_RECORD[n_steps, R]."""
+        R = self.n_trackers
+        r = np.ascontiguousarray(ranges, dtype=np.float32)
+        r = r.reshape(-1, R, r.shape[-1])
+        n_steps = r.shape[0]
+        hints, act = self._per_entry(n_steps, pose_hints, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_loc_process_many(
+            self.h, C.byref(scan), n_steps, r.shape[2], r.ctypes.data, r.shape[2], None if hints is None else hints.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_points(self, containers, pose_hints=None, active=None, counts=None) -> np.ndarray:
+        """containers[step][tracker]: (n, 2) float32 arrays in level-0 cell units (None or empty where the entry is not
+        active), or -- with `counts` [n_steps, R] -- one packed array in step-major order."""
+        R = self.n_trackers
+        if counts is None:
+            flat = [np.zeros((0, 2), np.float32) if p is None else np.asarray(p, dtype=np.float32).reshape(-1, 2)
+                    for row in containers for p in row]
+            assert len(flat) % R == 0, "every step needs one container per tracker"
+            counts = np.array([len(p) for p in flat], dtype=np.int32)
+            pts = np.concatenate(flat) if flat else np.zeros((0, 2), np.float32)
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+            pts = np.asarray(containers, dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        n_steps = len(counts) // R
+        hints, act = self._per_entry(n_steps, pose_hints, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_loc_process_many_points(
+            self.h, n_steps, pts.ctypes.data, counts.ctypes.data, None if hints is None else hints.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_clouds(self, xyz, scan: HectorScan, valid=None, take=None, pose_hints=None, active=None) -> np.ndarray:
+        """xyz: [n_steps, R, n_points, 3] float32 clouds in the de-skew's layout, valid [n_steps, R, n_points] or None = every
+        point, take [n_steps, R] or None = every entry -> HECTOR_RECORD[n_steps, R]."""
+        R = self.n_trackers
+        x = np.ascontiguousarray(xyz, dtype=np.float32)
+        if x.ndim != 4 or x.shape[1] != R or x.shape[3] != 3:
+            raise ValueError("xyz must be [n_steps, R, n_points, 3]")
+        n_steps, npts = x.shape[0], x.shape[2]
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid).astype(bool).astype(np.uint8)).reshape(n_steps, R, npts)
+        t = None if take is None else np.ascontiguousarray(np.asarray(take).astype(bool).astype(np.uint8)).reshape(n_steps, R)
+        hints, act = self._per_entry(n_steps, pose_hints, active)
+        out = np.zeros((n_steps, R), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_loc_process_many_clouds(
+            self.h, C.byref(scan), n_steps, npts, x.ctypes.data, None if v is None else v.ctypes.data,
+            None if t is None else t.ctypes.data, None if hints is None else hints.ctypes.data,
+            None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
+
+    def process_many_clouds_dev(self, n_steps: int, n_points: int, xyz_ptr: int, valid_ptr, take_ptr, take_stride: int,
+                                scan: HectorScan, pose_hints=None, active=None) -> np.ndarray:
+        """The same on clouds in HBM: xyz [n_steps * R, n_points, 3] float32, valid uint8 or None, take_ptr int32 words
+        take_stride apart or None; entry i is taken iff it is active and word i * take_stride is > 0 -- the `status` field of
+        an MSYNC_RECORD array with take_stride = MSYNC_RECORD.itemsize // 4 serves as it stands."""
+        hints, act = self._per_entry(int(n_steps), pose_hints, active)
+        out = np.zeros((int(n_steps), self.n_trackers), HECTOR_RECORD)
+        self.ctx.check(self.L.lslam_hector_loc_process_many_clouds_dev(
+            self.h, C.byref(scan), int(n_steps), int(n_points), xyz_ptr, valid_ptr, take_ptr, int(take_stride),
+            None if hints is None else hints.ctypes.data, None if act is None else act.ctypes.data, out.ctypes.data))
+        return out
 
 
 class GMappingMap:

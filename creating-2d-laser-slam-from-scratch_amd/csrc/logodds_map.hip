@@ -3431,6 +3431,46 @@ void* lslam_map_cells_dev_ptr(lslam_map* map, int level) {
   return map->levels[level].d_logodds;
 }
 
+// The inverse of the two readers above.  Only the float plane changes.  The key planes stay: a key is (epoch << 16 | beam) of
+// the scan that set it, a scan reads a key as "touched by me" only where its epoch is the scan's own, and the next scan's
+// epoch is larger than every epoch in the planes (clear_marks zeroes them where the epochs wrap) -- so after the pending apply
+// below has gone out, every cell is untouched for whatever scan comes next, as in the reference's map after a completed
+// updateByScan (updateIndex < currMarkFreeIndex everywhere).
+int lslam_map_write_logodds(lslam_map* map, int level, const float* src) {
+  if (!map || !src || level < 0 || level >= (int)map->levels.size()) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  Level& L = map->levels[level];
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  {
+    int rc = flush_pending(map);
+    if (rc) return rc;
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(L.d_logodds, src, (size_t)L.sx * L.sy * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  LSLAM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // src is the caller's again
+  return LSLAM_OK;
+}
+
+int lslam_map_write_logodds_dev(lslam_map* map, int level, const float* src_dev) {
+  if (!map || !src_dev || level < 0 || level >= (int)map->levels.size()) return LSLAM_ERR_INVALID_ARGUMENT;
+  lslam_context* ctx = map->ctx;
+  Level& L = map->levels[level];
+  LSLAM_HIP(ctx, hipSetDevice(ctx->device));
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, src_dev) != hipSuccess) {  // an address the runtime has never heard of: host memory
+    (void)hipGetLastError();
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_map_write_logodds_dev: the source is not device memory");
+  }
+  if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
+    return ctx->fail(LSLAM_ERR_INVALID_ARGUMENT, "lslam_map_write_logodds_dev: the source is not device memory");
+  if (src_dev == L.d_logodds) return flush_pending(map);  // a plane written onto itself
+  {
+    int rc = flush_pending(map);
+    if (rc) return rc;
+  }
+  LSLAM_HIP(ctx, hipMemcpyAsync(L.d_logodds, src_dev, (size_t)L.sx * L.sy * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  return LSLAM_OK;
+}
+
 // Enqueue whatever a single-scan update still owes the float planes (the deferred apply of the pipelined path).
 // lslam_map_read_*, lslam_map_match_*, the batched update and lslam_synchronize do this themselves; a caller that reads
 // the plane behind lslam_map_cells_dev_ptr from its OWN stream calls it before recording its event on lslam_stream().
@@ -4660,3 +4700,6 @@ int lslam_hector_fleet_stats(const lslam_hector_fleet* f, int64_t out[6]) {
 }
 
 }  // extern "C"
+
+
+#include "hector_loc_impl.hpp"  // lslam_hector_loc_*: R trackers on one borrowed map

@@ -439,6 +439,13 @@ class MapRepGpu {
   // getGridMap(level) contents: log-odds plane / the int8 data of nav_msgs::OccupancyGrid
   void readLogOdds(int level, float* out) { lslam_map_read_logodds(h_, level, out); }
   void readOccupancy(int level, int8_t* out) { lslam_map_read_occupancy_i8(h_, level, out); }
+  // the inverse of readLogOdds: a saved plane back in, or -- writeLogOddsDev with another map's plane in HBM -- a snapshot
+  void writeLogOdds(int level, const float* plane) {
+    if (lslam_map_write_logodds(h_, level, plane) != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  void writeLogOddsDev(int level, const float* planeDev) {
+    if (lslam_map_write_logodds_dev(h_, level, planeDev) != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
   lslam_map* handle() { return h_; }
 
  private:
@@ -679,6 +686,88 @@ class HectorSlamFleetGpu {
   std::vector<float> pts_, origos_, hints_;
   std::vector<int32_t> counts_;
   std::vector<uint8_t> flags_, active_;
+};
+
+// R robots LOCALISING on one finished map (lslam_hector_loc_*): per robot and scan, HectorSlamProcessor::update (:81-108) with
+// the gate never firing -- matchData from the hint or the robot's own last pose, lastScanMatchPose / lastScanMatchCov set, no
+// updateByScan.  The map is borrowed and only read: it must outlive the localiser, and may be changed through its own methods
+// (or a HectorSlamProcessorGpu on it) between calls.  A call costs 2 launches per chunk of steps (1 in the container form)
+// whatever size() is, and one host wait.
+class HectorLocalizerGpu {
+ public:
+  HectorLocalizerGpu(lslam_context* ctx, MapRepGpu& map, int nTrackers) : ctx_(ctx), n_(nTrackers) {
+    check(lslam_hector_loc_create(map.handle(), nTrackers, &h_));
+  }
+  ~HectorLocalizerGpu() { lslam_hector_loc_destroy(h_); }
+  HectorLocalizerGpu(const HectorLocalizerGpu&) = delete;
+  HectorLocalizerGpu& operator=(const HectorLocalizerGpu&) = delete;
+
+  int size() const { return n_; }
+  // lastScanMatchPose of trackers first .. first + count - 1 (x, y, heading each); after construction: zero
+  void setPoses(int first, int count, const float* posesXYH) { check(lslam_hector_loc_set_poses(h_, first, count, posesXYH)); }
+  void getLastScanMatchPose(int tracker, float out[3]) { check(lslam_hector_loc_state(h_, tracker, out, nullptr)); }
+  void getLastScanMatchCovariance(int tracker, float out[9]) { check(lslam_hector_loc_state(h_, tracker, nullptr, out)); }
+  void setMaxStepsPerLaunch(int steps) { check(lslam_hector_loc_set_option(h_, LSLAM_HECTOR_LOC_OPT_MAX_STEPS_PER_LAUNCH, steps)); }
+
+  // one step in the reference's shapes: dataContainers[r] is tracker r's (getSize() / getVecEntry(i)); poseHintsWorld[r]
+  // indexable by [0..2], or nullptr: every tracker starts from its own last pose.  active: size() flags or nullptr = all.
+  template <typename Container, typename Pose>
+  void update(const Container* dataContainers, const Pose* poseHintsWorld = nullptr, const bool* active = nullptr,
+              lslam_hector_record* records = nullptr) {
+    pts_.clear();
+    counts_.assign((size_t)n_, 0);
+    hints_.assign((size_t)3 * n_, 0.f);
+    active_.assign((size_t)n_, 1);
+    for (int r = 0; r < n_; ++r) {
+      if (active && !active[r]) {
+        active_[(size_t)r] = 0;
+        continue;
+      }
+      const Container& c = dataContainers[r];
+      counts_[(size_t)r] = c.getSize();
+      for (int i = 0; i < c.getSize(); ++i) {
+        pts_.push_back(c.getVecEntry(i)[0]);
+        pts_.push_back(c.getVecEntry(i)[1]);
+      }
+      for (int q = 0; q < 3 && poseHintsWorld; ++q) hints_[(size_t)3 * r + q] = poseHintsWorld[r][q];
+    }
+    if (pts_.empty()) pts_.resize(2);
+    updateMany(1, pts_.data(), counts_.data(), poseHintsWorld ? hints_.data() : nullptr, active ? active_.data() : nullptr, records);
+  }
+  // nSteps steps; every per-entry array indexed step * size() + tracker, as the lslam_hector_loc_process_many* calls take them
+  void updateMany(int nSteps, const float* pointsXY, const int32_t* nPoints, const float* poseHints, const uint8_t* active,
+                  lslam_hector_record* records) {
+    check(lslam_hector_loc_process_many_points(h_, nSteps, pointsXY, nPoints, poseHints, active, records));
+  }
+  void updateManyScans(const lslam_hector_scan& scan, int nSteps, int nReadings, const float* ranges, int rangesStride,
+                       const float* poseHints, const uint8_t* active, lslam_hector_record* records) {
+    check(lslam_hector_loc_process_many(h_, &scan, nSteps, nReadings, ranges, rangesStride, poseHints, active, records));
+  }
+  void updateManyClouds(const lslam_hector_scan& scan, int nSteps, int nPoints, const float* xyz, const uint8_t* valid,
+                        const uint8_t* take, const float* poseHints, const uint8_t* active, lslam_hector_record* records) {
+    check(lslam_hector_loc_process_many_clouds(h_, &scan, nSteps, nPoints, xyz, valid, take, poseHints, active, records));
+  }
+  // clouds in HBM, entry-major; takeDev: int32 words takeStride apart (lslam_msync_record::status at 22), or nullptr
+  void updateManyCloudsDev(const lslam_hector_scan& scan, int nSteps, int nPoints, const float* xyzDev, const uint8_t* validDev,
+                           const int32_t* takeDev, int takeStride, const float* poseHints, const uint8_t* active,
+                           lslam_hector_record* records) {
+    check(lslam_hector_loc_process_many_clouds_dev(h_, &scan, nSteps, nPoints, xyzDev, validDev, takeDev, takeStride, poseHints,
+                                                   active, records));
+  }
+  // {steps, tracker-scans matched, calls, host waits, kernel launches, launches of the tracking kernel}
+  void stats(int64_t out[6]) const { lslam_hector_loc_stats(h_, out); }
+  lslam_hector_loc* handle() { return h_; }
+
+ private:
+  void check(int rc) {
+    if (rc != LSLAM_OK) throw std::runtime_error(lslam_last_error(ctx_));
+  }
+  lslam_context* ctx_;
+  int n_;
+  lslam_hector_loc* h_ = nullptr;
+  std::vector<float> pts_, hints_;
+  std::vector<int32_t> counts_;
+  std::vector<uint8_t> active_;
 };
 
 // LidarUndistortion::CorrectLaserScan (lesson5/src/lidar_undistortion.cc:339-447) for many scans per launch.  The caller

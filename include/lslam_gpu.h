@@ -1044,6 +1044,67 @@ int lslam_hector_fleet_process_many_synced(lslam_hector_fleet* f, struct lslam_m
 int lslam_hector_fleet_sync_stats(const lslam_hector_fleet* f, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
+/* Hector localisation: write a pyramid level; track R robots on ONE finished map per launch   */
+/* ---------------------------------------------------------------------------------------- */
+/* The inverse of lslam_map_read_logodds / lslam_map_cells_dev_ptr: sx*sy floats, row-major y*size_x+x, copied bit for bit (NaN,
+ * +-inf and -0.0 included).  Like every reader the call first enqueues a pending pipelined apply; the cached and resident
+ * containers, the update factors and every counter stay as they were.  The per-cell "touched by this scan" marks need no
+ * reset: they carry the epoch of the scan that made them, and every later scan compares against a larger one.
+ * The host form returns when the plane is written; the _dev form is asynchronous on lslam_stream(), and another map's
+ * lslam_map_cells_dev_ptr of the same context and level size is a legal source (the device-to-device snapshot).
+ * LSLAM_ERR_INVALID_ARGUMENT, map unchanged: a NULL pointer, a level out of range, a _dev source the runtime knows not to be
+ * device memory. */
+int lslam_map_write_logodds(lslam_map* map, int level, const float* src_host);
+int lslam_map_write_logodds_dev(lslam_map* map, int level, const float* src_dev);
+
+/* R trackers on one BORROWED map (destroy the localiser first).  A taken entry is HectorSlamProcessor::update (:81-108) with the
+ * gate never firing: newPose = matchData(hint or lastScanMatchPose, container); lastScanMatchPose / lastScanMatchCov set; no
+ * updateByScan -- bit for bit the records and state of a lslam_hector processor on the same map with both thresholds +inf, run
+ * alone over the tracker's taken entries, whenever both launch the same form of the matcher (the form follows the capacity of
+ * the CALL and the map's LSLAM_GN_THREADS, as the streamed processor's).  The map is only read: every plane, the cached and
+ * resident containers, their origo and lslam_map_cached_points are what they were; between calls the map may change through
+ * any lslam_map_* / lslam_hector_* call, and the next call sees it as it then is.
+ * Indexing is the fleet's: entry i = step * R + tracker for the ranges rows, the containers (back to back), pose_hints[i][3],
+ * active[i], out[i] and the take words.  pose_hints NULL: every tracker chains from its own last pose; active NULL: all
+ * active.  An entry is taken iff it is active and -- cloud forms -- its take flag / word is > 0 (lslam_msync_record::status
+ * with take_stride = sizeof(lslam_msync_record) / 4 serves as it stands).  An entry that is not taken changes nothing of its
+ * tracker; its record is all zero with n_points = -1.  `updated` is always 0.  An empty container returns the start pose and
+ * leaves the covariance as it was (ScanMatcher.h:96).
+ * A call is cut into chunks of LSLAM_HECTOR_LOC_OPT_MAX_STEPS_PER_LAUNCH steps (0 = the default: as many as keep the chunk's
+ * container block within 64 MiB, at least 1); a chunk is 2 launches (containers of every entry; one block per tracker walking
+ * its entries in step order), 1 in the container form, whatever R and the steps are, and chunking changes no bit.  ONE host
+ * synchronisation per call, plus one in a ranges-form call that meets a new scan geometry.
+ * LSLAM_ERR_INVALID_ARGUMENT (no device needed): NULL handles or required arrays, n_trackers < 1, negative counts, first /
+ * count out of range, n_readings < 1 in the ranges form, a container-form entry with active == 0 and n_points != 0.
+ * LSLAM_ERR_UNSUPPORTED: LSLAM_MAP_OPT_ORDERED_SUMS maps, more than 8 levels, more than 65536 readings or points per scan,
+ * more than 65535 trackers.  n_steps == 0 is LSLAM_OK and does nothing. */
+typedef struct lslam_hector_loc lslam_hector_loc;
+enum { LSLAM_HECTOR_LOC_OPT_MAX_STEPS_PER_LAUNCH = 1 };
+int lslam_hector_loc_create(lslam_map* map, int n_trackers, lslam_hector_loc** out);
+void lslam_hector_loc_destroy(lslam_hector_loc* l);
+int lslam_hector_loc_size(const lslam_hector_loc* l);
+/* lastScanMatchPose of trackers first .. first+count-1 (after create: 0, 0, 0; lastScanMatchCov: zero) */
+int lslam_hector_loc_set_poses(lslam_hector_loc* l, int first, int count, const float* poses_xyh);
+int lslam_hector_loc_state(lslam_hector_loc* l, int tracker, float pose[3], float cov[9]);
+int lslam_hector_loc_set_option(lslam_hector_loc* l, int option, int value);
+int lslam_hector_loc_process_many(lslam_hector_loc* l, const lslam_hector_scan* scan, int n_steps, int n_readings,
+                                  const float* ranges, int ranges_stride, const float* pose_hints, const uint8_t* active,
+                                  lslam_hector_record* out);
+int lslam_hector_loc_process_many_points(lslam_hector_loc* l, int n_steps, const float* points_xy, const int32_t* n_points,
+                                         const float* pose_hints, const uint8_t* active, lslam_hector_record* out);
+int lslam_hector_loc_process_many_clouds(lslam_hector_loc* l, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                         const float* xyz, const uint8_t* valid, const uint8_t* take, const float* pose_hints,
+                                         const uint8_t* active, lslam_hector_record* out);
+/* clouds in HBM: xyz_dev [n_steps * R][n_points][3], valid_dev [n_steps * R][n_points] or NULL, take_dev int32 words
+ * take_stride apart or NULL */
+int lslam_hector_loc_process_many_clouds_dev(lslam_hector_loc* l, const lslam_hector_scan* scan, int n_steps, int n_points,
+                                             const float* xyz_dev, const uint8_t* valid_dev, const int32_t* take_dev,
+                                             int take_stride, const float* pose_hints, const uint8_t* active,
+                                             lslam_hector_record* out);
+/* out = {steps, tracker-scans matched, calls, waits for the stream, kernel launches, launches of the tracking kernel} */
+int lslam_hector_loc_stats(const lslam_hector_loc* l, int64_t out[6]);
+
+/* ---------------------------------------------------------------------------------------- */
 /* lesson5 lidar motion de-skew (LidarUndistortion::CorrectLaserScan, lesson5/src/            */
 /* lidar_undistortion.cc:339-447) -- SURVEY 8(f) #4.  Pinned (round 4) against the reference's */
 /* own source compiled in place behind ROS / tf / PCL / Eigen stand-ins (oracle/shim, which    */
